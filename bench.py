@@ -21,18 +21,21 @@ phase throughput-bound, one call of 512 images beats two of 256 in flight at the
 Scaling is weak: every rank processes its own `--batch` images per step; ranks exchange one all-gather
 of the decoded (padded) sequences per engine call, as a real image-sharded deployment would.
 
-Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize pairs, MAX over ranks.  A K-step region
-shorter than --min-seconds is REPEATED (each repetition bracketed the same way) until that much time has been
-measured; `value` comes from the MEDIAN repetition and the spread is reported (`timing`).  Every engine call is also
-bracketed with HIP events on its lane stream (`engine_call_ms`: median / p10 / p90).  Steps use DISTINCT images (a
-resident pool of `coalesce` batches).  Two more measured legs on rank 0: `batch8` = the same steps with coalesce 1
-(every 8-image batch its own engine call: BASELINE config 2's literal batch), and `eos_run` = EOS honoured instead of
-forced instance counts.
+Timing: W warm-up steps, then EXACTLY K steps between barrier + synchronize pairs, MAX over ranks; `ms_per_step` is that
+region's time over K.  With --min-seconds S the K-step region is REPEATED (each repetition bracketed the same way) until S
+seconds have been measured; `value` then comes from the MEDIAN repetition and the spread is reported (`timing`).  Every
+engine call is also bracketed with HIP events on its lane stream (`engine_call_ms`: median / p10 / p90).  Steps use
+DISTINCT images (a resident pool of `coalesce` batches).
 
-One JSON line on rank 0: images/s (whole job), chars/s, ms per step, `roofline` = the dominant kernel class by GPU time
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR: the last
+timed step's decoded ids and probabilities as DIR/<name>.npy, float32) and one JSON line on rank 0: images/s (whole job),
+chars/s, ms per step.  --full adds everything else: the measured legs on rank 0 -- `batch8` = the same steps with coalesce
+1 (every 8-image batch its own engine call: BASELINE config 2's literal batch), `eos_run` = EOS honoured instead of forced
+instance counts, the parity engine and BASELINE configs 3 / 4 / 5 -- `roofline` = the dominant kernel class by GPU time
 (large-M GEMMs against the 2.5 PFLOP/s bf16 matrix-core peak, or the decoder cross-attention against 8 TB/s), the other
 classes under `roofline_other`, all timed live with HIP events on their launch streams, and the CPU baseline (the oracle
 = reference algorithm restated on CPU, timed on a bounded sample of the same workload, scaled as its `sample` says).
+The --no-* switches turn single parts of --full off.
 """
 import argparse
 import ctypes
@@ -61,7 +64,12 @@ def parse():
                         'are -- ONE on a 1-GPU box: launch under torch.distributed.run exactly as the driver launches N > 1')
     p.add_argument('--steps', type=int, default=192)
     p.add_argument('--warmup', type=int, default=32)
-    p.add_argument('--min-seconds', type=float, default=5.0, help='repeat the K-step timed region until this much time is measured')
+    p.add_argument('--full', action='store_true',
+                   help='also run everything beyond the headline: the batch8 / eos_run / parity / config legs, the rooflines and the CPU baseline')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)')
+    p.add_argument('--min-seconds', type=float, default=None,
+                   help='repeat the K-step timed region until this much time is measured (default: one region; the --full legs: 5)')
     p.add_argument('--no-batch8', action='store_true', help='skip the coalesce-1 (true batch-8 engine calls) leg')
     p.add_argument('--no-eos-run', action='store_true', help='skip the EOS-honouring leg')
     p.add_argument('--eos-pt-len', type=int, default=130, help='pt_seq_length of the EOS-honouring leg (<= 64 instances per image)')
@@ -342,7 +350,7 @@ def _timed_loop(a, world, device, step):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         reps.append(el)
-        stop = 1.0 if (sum(reps) >= a.min_seconds or len(reps) >= 64) else 0.0
+        stop = 1.0 if (sum(reps) >= (a.min_seconds or 0.0) or len(reps) >= 64) else 0.0
         if world > 1:
             t = torch.tensor([stop], device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -394,6 +402,11 @@ def run_mgp_str(a, device, world, rank):
             last['ids'] = model.greedy(pool[i % 2])
     with torch.cuda.stream(stream):
         el, reps = _timed_loop(a, world, device, step)
+        if a.dump_outputs and rank == 0:
+            torch.cuda.synchronize()
+            names = ('char', 'bpe', 'wp')
+            dump_outputs(a.dump_outputs, dict([(n + '_ids', i) for n, (i, _) in zip(names, last['ids'])] +
+                                              [(n + '_prob', p_) for n, (_, p_) in zip(names, last['ids'])]))
         roof = _class_roofline(_lib.lib(), 1, lambda: [step(i) for i in range(2)],
                                'gemm_256 / gemm_dma (ViT-B q / k / v / proj / fc1 / fc2, A^3 modules, vocabulary heads)', MFMA_PEAK_TFS, 'TFLOP/s', 1e12) if not a.no_roofline else None
     wps = world * B * a.steps / el
@@ -578,8 +591,25 @@ class StepLoop(object):
         return [float(v) for v in allr.tolist()]
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (the ids are exact: they are far below 2^24)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().float().cpu().contiguous().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > 64 << 20:
+        raise SystemExit('--dump-outputs: %d bytes of outputs, more than 64 MB' % total)
+    for k, v in host.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+
+
 def main():
     a = parse()
+    if not a.full:
+        # a plain run measures the headline alone; the --no-* switches below only matter under --full
+        a.no_batch8 = a.no_eos_run = a.no_parity_leg = a.no_config_legs = a.no_roofline = a.no_cpu_baseline = True
+    if a.dump_outputs and a.workload == 'kie':
+        raise SystemExit('--dump-outputs: the spotting and mgp_str workloads (kie returns per-image entity records, not arrays)')
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(a.gpus))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -690,8 +720,14 @@ def main():
         del calls[:]
         del gather_ev[:]
         del local_s[:]
-        reps, out = loop.repeat(a.steps, a.min_seconds, 64, forced='N')
+        reps, out = loop.repeat(a.steps, a.min_seconds or 0.0, 64, forced='N')
         torch.cuda.synchronize()
+        if a.dump_outputs and rank == 0:
+            # the last timed step = the last `B` images of every rank's share of the last engine call's all-gathered result
+            last_g = a.steps % G or G
+            ids_, probs_ = out
+            dump_outputs(a.dump_outputs, dict(ids=ids_.reshape(world, last_g * B, *ids_.shape[1:])[:, -B:].reshape(world * B, *ids_.shape[1:]),
+                                              probs=probs_.reshape(world, last_g * B, *probs_.shape[1:])[:, -B:].reshape(world * B, *probs_.shape[1:])))
         call_ms = [e0.elapsed_time(e1) for e0, e1, _ in calls]
         call_imgs = calls[0][2] if calls else B * G
     elapsed = pct(reps, 0.5)
@@ -705,6 +741,7 @@ def main():
     assert ids.shape[0] == world * B * last_g and int((ids[:, :, 34:] >= args.num_bins).all()), 'decode output malformed'
 
     extra = {}
+    leg_seconds = 5.0 if a.min_seconds is None else a.min_seconds   # the batch8 / eos_run legs' own repetition budget (--full)
     def leg(name, fn):
         try:
             extra[name] = fn()
@@ -724,7 +761,7 @@ def main():
             r8 = []
             # two lanes of 8-image calls interleave differently from run to run (96 .. 139 img/s over four 128-step runs,
             # profiles/r02zb): several short repetitions, median and spread reported
-            while (sum(r8) < min(a.min_seconds, 6.0) or len(r8) < 4) and len(r8) < 12:
+            while (sum(r8) < min(leg_seconds, 6.0) or len(r8) < 4) and len(r8) < 12:
                 r8.append(timed(k8, group=1)[0])
         e8 = pct(r8, 0.5)
         pools['active'] = pool
@@ -750,7 +787,7 @@ def main():
                 torch.cuda.synchronize()
                 del inst_log[:]
                 re_ = []
-                while (sum(re_) < min(a.min_seconds, 4.0) or len(re_) < 3) and len(re_) < 10:
+                while (sum(re_) < min(leg_seconds, 4.0) or len(re_) < 3) and len(re_) < 10:
                     re_.append(timed(ke, group=1, forced=None)[0])
                 n_inst = torch.cat(inst_log).tolist()
             ee = pct(re_, 0.5)
@@ -909,6 +946,7 @@ def main():
     def side_args(**kw):
         b_ = argparse.Namespace(**vars(a))
         b_.steps, b_.warmup, b_.min_seconds, b_.no_roofline, b_.no_cpu_baseline, b_.batch = 3, 1, 1.5, True, True, None
+        b_.dump_outputs = None
         for k_, v_ in kw.items():
             setattr(b_, k_, v_)
         return b_

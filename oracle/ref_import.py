@@ -1,8 +1,7 @@
 """TEST INFRASTRUCTURE -- load the *real* reference OmniParser model classes on CPU.
 
-Only usable where /root/reference exists (the build container).  Used by gen_golden.py to
-produce tests/golden/* and by the `not gpu` tests that pin oracle/omniparser_ref.py against the
-reference itself.  Nothing on the GPU box imports this module.
+Only usable where the reference tree exists (REF_ROOT).  Used by gen_golden.py and gen_golden_pins.py
+to produce tests/golden/*; the tests read those fixtures and never import this module.
 
 The reference needs three helpers from `timm.models.layers` (swin_transformer.py:14) and imports
 `torchvision` (utils/nested_tensor.py:2, backbone/resnet.py:2,7); neither package is installed,

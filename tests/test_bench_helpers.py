@@ -159,3 +159,26 @@ def test_rocpd_rate_bins_dispatches_per_window(tmp_path, capsys):
     assert lines[0] == ['t_ms', 'dispatches', 'kernels/ms', 'concurrency', 'queues', 'marker']
     assert lines[1] == ['0', '4', '0.2', '1.00', '2', '0']
     assert lines[2] == ['20', '1', '0.1', '0.05', '1', '1']
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """a plain line times exactly --steps steps once and writes no outputs; --full and --dump-outputs are opt-in"""
+    b = _bench()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    a = b.parse()
+    assert not a.full and a.dump_outputs is None and a.min_seconds is None
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out', '--min-seconds', '5'])
+    a = b.parse()
+    assert a.full and a.dump_outputs == 'out' and a.min_seconds == 5.0
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    ids = torch.arange(24, dtype=torch.int32).view(2, 3, 4)
+    probs = torch.rand(2, 3, 5)
+    b.dump_outputs(str(tmp_path / 'd'), dict(ids=ids, probs=probs))
+    x, p = np.load(str(tmp_path / 'd' / 'ids.npy')), np.load(str(tmp_path / 'd' / 'probs.npy'))
+    assert x.dtype == np.float32 and x.shape == (2, 3, 4) and np.array_equal(x, ids.numpy().astype(np.float32))
+    assert p.dtype == np.float32 and np.array_equal(p, probs.numpy())

@@ -1,5 +1,5 @@
-"""MGP-STR oracle (oracle/mgp_str_ref.py) pinned to the reference: golden fixture (always) and the reference's own
-code (where /root/reference exists); host-side pieces of the MGP-STR engine that need no GPU."""
+"""MGP-STR oracle (oracle/mgp_str_ref.py) pinned to the reference: golden fixture and what the reference's own code computed
+on a fresh case (tests/golden/reference_pins_mgp.pt); host-side pieces of the MGP-STR engine that need no GPU."""
 import os
 
 import pytest
@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 from oracle import gen_golden_mgp as G
 from oracle import mgp_str_ref as R
-from oracle import ref_import_mgp as I
+from oracle import gen_golden_pins as P
 
 
 def _close(a, b, tol):
@@ -33,28 +33,26 @@ def test_oracle_matches_reference_fixture(golden_dir):
         assert _close(got[name + '_prob'], ref[name + '_prob'], 1e-4)
 
 
-@pytest.mark.skipif(not I.available(), reason='reference tree / transformers port not present')
-def test_fresh_case_against_reference_code():
-    """different depth / seed than the fixture, through the reference's MGPSTR.forward and the REAL TokenLearner"""
-    c = R.cfg(depth=3)
-    sd = R.make_state_dict(c, seed=5)
-    model = I.build_reference_model(c, sd)
-    img = torch.rand(3, 3, 32, 128, generator=torch.Generator().manual_seed(6)) * 2 - 1
+def test_fresh_case_against_reference_code(golden_dir):
+    """different depth / seed than the fixture, against what the reference's MGPSTR.forward and the REAL TokenLearner computed on
+    the same inputs (tests/golden/reference_pins_mgp.pt, oracle/gen_golden_pins.py); both sides in float64, so that the gates
+    measure the restatement and not the host's fp32 rounding"""
+    c, sd, img, x = P.mgp_fresh_case()
+    ref = {k: ([t.double() for t in v] if isinstance(v, list) else v.double())
+           for k, v in torch.load(os.path.join(golden_dir, 'reference_pins_mgp.pt'), weights_only=False)['mgp_fresh'].items()}
+    # the wide heads are the reference's nn.Linear on the inputs it recorded (their logits are too large to store)
+    ref_out = [ref['attens'], ref['char']] + [F.linear(ref[n + '_head_in'], sd['mgp_str.%s_head.weight' % n], sd['mgp_str.%s_head.bias' % n])
+                                             for n in ('bpe', 'wp')]
     with torch.no_grad():
-        ref = model(img, is_eval=True)
         mine = R.forward(sd, c, img)
         # the A^3 restatement against the reference class alone, on an arbitrary token tensor
-        TL = I.token_learner_class()
-        tl = TL(c['embed'], c['max_len']).eval()
-        tl.load_state_dict({k[len('mgp_str.bpe_tokenLearner.'):]: v for k, v in sd.items() if k.startswith('mgp_str.bpe_tokenLearner.')})
-        x = torch.randn(2, 257, c['embed'], generator=torch.Generator().manual_seed(7))
-        sel_ref, out_ref = tl(x)
         sel, out = R.token_learner(sd, c, x, 'bpe')
-    for a, b in zip(ref[0], mine[0]):
+    assert len(ref_out[0]) == len(mine[0]) == 3 and ref_out[1].shape[0] == img.shape[0] and mine[1].dtype == torch.float64
+    for a, b in zip(ref_out[0], mine[0]):
         assert _close(a, b, 1e-6)
-    for a, b in zip(ref[1:], mine[1:]):
-        assert _close(a, b, 1e-4)
-    assert _close(sel, sel_ref, 1e-6) and _close(out, out_ref, 1e-5)
+    for a, b in zip(ref_out[1:], mine[1:]):
+        assert a.shape == b.shape and _close(a, b, 1e-4)
+    assert _close(sel, ref['sel'], 1e-6) and _close(out, ref['tl_out'], 1e-5)
 
 
 def _crafted_logits(ids_rows, V, hi=9.0):

@@ -5,7 +5,7 @@
 # Legs (environment knobs in brackets):
 #   smoke            __graft_entry__.smoke()
 #   tests            the whole GPU suite                 [TESTS_K: a pytest -k expression; TESTS_TIMEOUT]
-#   bench            the driver's bench command          [BENCH_ARGS, default "--steps 20 --warmup 5 --phase-times"]
+#   bench            the full bench line (--full)        [BENCH_ARGS, default "--steps 20 --warmup 5 --phase-times"]
 #   prof:<engine>    rocprofv3 --kernel-trace --stats of the bench command, eager launches, one engine (bf16 | bf16x3) -> kernel_stats / kernel_shapes
 #   probe            tools/build/probe_stream (weight-stream rate of one compute unit, csrc/dec_rows.hip's inner loop alone)
 #   libgemm          hipBLASLt next to gemm_256 / gemm_4w_p on the K >= 1024 products: kernel trace (name, grid, LDS, registers) + SQ / TCP counters
@@ -40,7 +40,7 @@ pmc_pass() {   # <name> <kernel substrings, comma separated> <command...> -- cou
 for leg in "$@"; do case $leg in
 smoke)  timeout 300 python __graft_entry__.py smoke > $OUT/smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/rc.log; tail -2 $OUT/smoke.txt;;
 tests)  OMP355_PARITY_REPORT=$OUT/parity_report.json timeout ${TESTS_TIMEOUT:-1500} python -m pytest tests -m gpu -q ${TESTS_K:+-k "$TESTS_K"} > $OUT/tests.log 2>&1; echo "tests rc=$?" >> $OUT/rc.log; tail -8 $OUT/tests.log;;
-bench)  timeout 900 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5 --phase-times} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/rc.log
+bench)  timeout 900 python bench.py --full ${BENCH_ARGS:---steps 20 --warmup 5 --phase-times} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/rc.log
         tail -3 $OUT/bench.err; python tools/bench_summary.py $OUT/bench.json;;
 prof:*) eng=${leg#prof:}
         (cd /tmp && timeout 420 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof_$eng -o ks -- python $R/bench.py --dtype $eng ${PROF_ARGS:---steps 20 --warmup 5} --min-seconds 0 --no-parity-leg --no-config-legs --no-batch8 --no-eos-run --no-cpu-baseline --no-roofline --graph 0 > $R/$OUT/prof_bench_$eng.json 2> $R/$OUT/prof_$eng.err); echo "prof $eng rc=$?" >> $OUT/rc.log
