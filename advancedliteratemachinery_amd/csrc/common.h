@@ -75,6 +75,7 @@ struct omp_ctx {
   int cross_nt = 1;          // non-temporal K / V^T loads: 1 = always (the slabs are read once per launch and would evict the decoder weights from the
                              // MALL: 8-image point phase 39.8 -> 37.2 ms, profiles/r03f_ab_*), 2 = only from 32 groups per launch (round 2), 0 = never
   int self_attn_impl = 0;    // 0 auto, 1 one wave per (row, head), 2 one wave per row
+  int sample_impl = 0;       // omp_head_softmax_mask_argmax: 0 auto, 1 wave per row, 2 row in registers, 3 workgroup per row + ticket (omp_debug_sample_impl)
   int dec_fused = 0;         // 0 = fused few-row decoder kernels where they apply (csrc/decoder.hip: fused_step_ok), 1 = the launch-per-op path everywhere
   int swin_impl = 0;         // 0 matrix cores, 1 scalar cross-check kernel, 2 matrix cores with per-score table lookups
   int mlp_variant = 0;       // alternative instantiations of the fused MLP; 100 = traced default

@@ -1145,6 +1145,9 @@ __global__ __launch_bounds__(256) void dec_cross_merge_kernel(const float* __res
 
 // ---------------------------------------------------------------------------------------------
 // greedy sampling: softmax over the support, candidate filter, argmax, probability. wave per row.
+// sample_underflow_rule (all three sampling kernels): the reference zeroes the non-candidates of the softmax and takes top-1 of what is
+// left.  When every candidate's probability is 0 (all candidates -inf, or a non-candidate above them all by more than expf's range) that
+// row is all zeros and torch's topk answers token 0 with probability 0 -- so do the kernels (and never emit their 0x7fffffff start index).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool is_candidate(const omp_sample_cfg& c, int tok, int i) {
   if (c.kind == OMP_DEC_PT) {
@@ -1191,8 +1194,10 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* __restrict
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
   if (lane == 0) {
+    float pb = expf(best - mx) / sum;
+    if (!(pb > 0.f)) { bi = 0; pb = 0.f; }   // see sample_underflow_rule
     seq[(int64_t)r * seq_ld + p + 1] = bi;
-    probs[(int64_t)r * seq_ld + p + 1] = expf(best - mx) / sum;
+    probs[(int64_t)r * seq_ld + p + 1] = pb;
     if (c.kind == OMP_DEC_PT && finished != nullptr) {
       // reference stops at the first EOS (transformer.py:126); later tokens of a finished row are ignored
       if (!finished[r] && bi == c.pt_eos) { finished[r] = 1; lengths[r] = p + 1; }
@@ -1248,8 +1253,10 @@ __global__ __launch_bounds__(256) void dec_sample_block_kernel(const float* __re
     __syncthreads();
     if (tid == 0) {
       sum = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+      float pb = expf(best - mx) / sum;
+      if (!(pb > 0.f)) { bi = 0; pb = 0.f; }   // see sample_underflow_rule
       seq[(int64_t)r * seq_ld + p + 1] = bi;
-      probs[(int64_t)r * seq_ld + p + 1] = expf(best - mx) / sum;
+      probs[(int64_t)r * seq_ld + p + 1] = pb;
       if (c.kind == OMP_DEC_PT && finished != nullptr) {
         if (!finished[r] && bi == c.pt_eos) { finished[r] = 1; lengths[r] = p + 1; }
       }
@@ -1312,8 +1319,10 @@ __global__ __launch_bounds__(256) void dec_sample_rows_kernel(const float* __res
       if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
     if (lane == 0) {
+      float pb = expf(best - mx) / sum;
+      if (!(pb > 0.f)) { bi = 0; pb = 0.f; }   // see sample_underflow_rule
       seq[(int64_t)r * seq_ld + p + 1] = bi;
-      probs[(int64_t)r * seq_ld + p + 1] = expf(best - mx) / sum;
+      probs[(int64_t)r * seq_ld + p + 1] = pb;
       if (c.kind == OMP_DEC_PT && finished != nullptr) {
         if (!finished[r] && bi == c.pt_eos) { finished[r] = 1; lengths[r] = p + 1; }
       }
@@ -1599,7 +1608,19 @@ extern "C" int omp_head_softmax_mask_argmax(const float* logits, int ld, int R, 
                                             int32_t* lengths, int32_t* d_pos, int advance, omp_stream_t s) {
   OMP_CHECK_ARG(logits && cfg && seq && probs && d_pos, "omp_head_softmax_mask_argmax: null pointer");
   OMP_CHECK_ARG(R > 0 && cfg->vocab > 0 && cfg->vocab <= ld, "omp_head_softmax_mask_argmax: bad shape");
-  if (R > sample_block_max_rows() && ld % 4 == 0 && ((uintptr_t)logits % 16) == 0 && cfg->vocab <= 2048)   // many rows: the row in registers (dec_sample_rows_kernel)
+  const int impl = omp_cur().sample_impl;
+  const bool rows_ok = ld % 4 == 0 && ((uintptr_t)logits % 16) == 0 && cfg->vocab <= 2048;
+  if (impl == 2 && !rows_ok) {
+    omp_set_error("omp_head_softmax_mask_argmax: sample impl 2 needs ld %% 4 == 0, 16-byte aligned rows and vocab <= 2048 (ld=%d vocab=%d)", ld, cfg->vocab);
+    return OMP_ERR_UNSUPPORTED;
+  }
+  if (impl == 3) {   // a workgroup per row; with advance the last one publishes pos + 1 (d_pos[1] is the ticket word, as in omp_decoder_plan)
+    hipLaunchKernelGGL(dec_sample_block_kernel, dim3(R), dim3(256), 0, (hipStream_t)s, logits, ld, R, *cfg, seq, probs, seq_ld, finished, lengths,
+                       d_pos, advance ? d_pos + 1 : (int32_t*)nullptr);
+    OMP_CHECK_LAUNCH("omp_head_softmax_mask_argmax");
+    return OMP_OK;
+  }
+  if (impl == 2 || (impl == 0 && R > sample_block_max_rows() && rows_ok))   // many rows: the row in registers (dec_sample_rows_kernel)
     hipLaunchKernelGGL(dec_sample_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, ld, R, *cfg, seq, probs, seq_ld, finished, lengths,
                        d_pos, (int32_t*)nullptr);
   else
@@ -1950,6 +1971,12 @@ int sample_and_advance(const omp_decoder_plan* P, hipStream_t st) {
 
 extern "C" int omp_debug_dec_fused(int mode) {
   omp_cur().dec_fused = mode == 1 ? 1 : 0;
+  return OMP_OK;
+}
+
+extern "C" int omp_debug_sample_impl(int which) {
+  OMP_CHECK_ARG(which >= 0 && which <= 3, "omp_debug_sample_impl: which must be 0..3 (got %d)", which);
+  omp_cur().sample_impl = which;
   return OMP_OK;
 }
 

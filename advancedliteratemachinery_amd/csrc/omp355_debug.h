@@ -49,6 +49,12 @@ int omp_debug_set_gemm_trace(void* buffer, int64_t n_workgroups);
 int omp_debug_swin_attn_impl(int which); /* 0 = matrix-core kernel (default), 1 = scalar cross-check kernel, 2 = matrix cores with per-score table lookups */
 int omp_debug_dec_fused(int mode);       /* 0 = fused few-row decoder step kernels where they apply (default), 1 = one launch per op everywhere (A/B, cross-check) */
 int omp_debug_self_attn_impl(int which); /* 0 auto, 1 = one wave per (row, head), 2 = one wave per row (all 8 heads) */
+/* kernel of omp_head_softmax_mask_argmax (omp_decoder_run keeps its own choice): 0 = auto (default: a wave per row, the row in registers beyond
+ * OMP355_SAMPLE_BLOCK_MAX_ROWS rows when ld % 4 == 0, the rows are 16-byte aligned and vocab <= 2048), 1 = a wave per row, 2 = the row in
+ * registers (OMP_ERR_UNSUPPORTED when those preconditions fail), 3 = a workgroup per row; with 3 and advance != 0 d_pos points to two int32
+ * (position, ticket = 0) as in omp_decoder_plan and the last workgroup publishes position + 1 and leaves the ticket at 0.  Other values:
+ * OMP_ERR_INVALID, selector unchanged */
+int omp_debug_sample_impl(int which);
 int omp_debug_rows_tile_choice(int R, int mid); /* host logic, no launch: rows per workgroup (16..80) a decoder row-owner launch of R rows takes; mid != 0: omp_dec_rows_mid (also 16 rows) */
 int omp_debug_rows_tile(int rtt);        /* decoder row-owner chains (bf16): rows per workgroup = 16 x rtt, 0 = chosen by row count (default), 2..5 forced */
 int omp_debug_cross_nt(int on);          /* non-temporal K / V^T loads in the cross-attention kernels: 1 = always (default), 2 = only from 32 groups per launch, 0 = never */

@@ -522,6 +522,13 @@ def dec_fused(mode):
     _lib.check(_lib.lib().omp_debug_dec_fused(int(mode)), 'omp_debug_dec_fused')
 
 
+def sample_impl(which):
+    """debug/testing: kernel of head_sample (omp_head_softmax_mask_argmax): 0 = auto (default), 1 = wave per row, 2 = the row in registers
+    (refused unless the row stride is a multiple of 4, the rows are 16-byte aligned and vocab <= 2048), 3 = workgroup per row; with 3 and
+    advance, d_pos holds (position, ticket = 0) and the kernel's last workgroup advances the position."""
+    _lib.check(_lib.lib().omp_debug_sample_impl(int(which)), 'omp_debug_sample_impl')
+
+
 def swin_attn_impl(which):
     """debug/testing: 0 = matrix-core window attention (default), 1 = scalar cross-check kernel, 2 = matrix cores with table lookups,
     3 = fp32 matrix cores also for split-pair output (the parity engine's call otherwise runs three bf16 products of split operands),

@@ -426,6 +426,11 @@ def check_sampling():
                     adv = abs(int(d_pos.item()) - (3 + step))
                     out.append(rec('sample[%s,vie%d,step%d,R=%d]' % (kind, vie, step, R), mism + adv + (0 if perr < 1e-5 else 1), 0,
                                    'perr=%.2e' % perr))
+                    # the first EOS of a point sequence finishes its row at length p + 1; poly / rec leave finished / lengths alone
+                    efin = (t_ref[:, 0] == a.pt_eos_index).to(torch.int32) if kind == 'pt' else torch.zeros(R, dtype=torch.int32)
+                    elen = efin * (3 + step)
+                    out.append(rec('sample[%s,vie%d,step%d,R=%d] finished / lengths' % (kind, vie, step, R),
+                                   int((fin.cpu() != efin).sum()) + int((lens.cpu() != elen).sum()), 0, '%d EOS rows' % int(efin.sum())))
     return out
 
 

@@ -308,6 +308,16 @@ def check_gemm_row_stats():
             out.append(rec('gemm_row_stats[%s %dx%dx%d] probabilities (relative)' % (tag, M, N, K), ((p0 - p1).abs() / p0).max().item(), 2e-6))
             if N > 200:
                 out.append(rec('gemm_row_stats[%s %dx%dx%d] the planted tie goes to the lower index' % (tag, M, N, K), float((i1 != 40).sum()) if tag == 'fp32' else 0.0, 0))
+            if N > 200:   # a higher exact tie inside the last, ragged 128-column tile (across its two 64-column halves where it is that wide)
+                t0 = (N - 1) // 128 * 128
+                Wd[N - 1] = Wd[t0 + 2]
+                bd[N - 1] = bd[t0 + 2] = 20.0
+                lg = ops.gemm(Ad, Wd, bd, out_dtype=torch.float32)
+                i0, _ = ops.row_argmax_prob(lg)
+                i1, _ = ops.gemm_row_argmax_prob(Ad, Wd, bd)
+                out.append(rec('gemm_row_stats[%s %dx%dx%d] tie %d = %d in the ragged last tile: ids identical' % (tag, M, N, K, t0 + 2, N - 1),
+                               float((i0 != i1).sum()), 0))
+                out.append(rec('gemm_row_stats[%s %dx%dx%d] ... and the lower index wins' % (tag, M, N, K), float((i1 != t0 + 2).sum()) if tag == 'fp32' else 0.0, 0))
         # bf16x3: split-pair activation rows against the [hi | hi | lo] image of the fp32 weight
         As, W3, bd = ops.split_bf16(A.to(DEV)), ops.split_weight3(W.to(DEV)), b.to(DEV)
         lg = ops.gemm(As, W3, bd, out_dtype=torch.float32, a_wrap=2 * K)

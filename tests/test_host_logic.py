@@ -779,3 +779,31 @@ def test_build_plan_is_by_content_and_audited_objects_need_proof():
         assert len(B.plan()[0]) == len(B.SOURCES)
     finally:
         B.FLAGS[:] = keep
+
+
+def test_sample_impl_selector_refuses_what_its_kernel_cannot_take():
+    """omp_debug_sample_impl (csrc/omp355_debug.h): 0..3 are accepted, anything else is OMP_ERR_INVALID; with the row-in-registers kernel
+    pinned (2), omp_head_softmax_mask_argmax refuses -- before any device access -- a row stride that is not a multiple of 4, rows that are
+    not 16-byte aligned and a vocabulary above 2048, instead of falling back to another kernel."""
+    import ctypes
+    import pytest
+    from advancedliteratemachinery_amd import _lib, ops
+    h = _lib.lib()
+    for bad in (-1, 4, 100):
+        assert h.omp_debug_sample_impl(bad) == -22
+    cfg = _lib.SampleCfg(_lib.DEC_REC, 1000, 1097, 1098, 1099, 1104, 0, 0, 0, 3)
+    big = _lib.SampleCfg(_lib.DEC_REC, 2000, 2097, 2098, 2099, 2104, 0, 0, 0, 3)
+    fake = ctypes.c_void_p(1 << 20)   # never dereferenced: every call below is refused by the host-side checks
+    cases = ((1107, 0, cfg), (1104, 4, cfg), (2104, 0, big))
+    try:
+        for v in range(4):
+            ops.sample_impl(v)
+        ops.sample_impl(2)
+        for ld, off, c in cases:
+            rc = h.omp_head_softmax_mask_argmax(ctypes.c_void_p((1 << 20) + off), ld, 8, ctypes.byref(c), fake, fake, 16, None, None, fake, 1, None)
+            assert rc == -95, (ld, off, rc)
+            assert b'sample impl 2' in h.omp_last_error()
+        with pytest.raises(RuntimeError):
+            ops.sample_impl(7)
+    finally:
+        ops.sample_impl(0)
