@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libomp355.so')
 
 OMP_F32, OMP_BF16, OMP_BF16X2 = 0, 1, 2   # BF16X2: split-bf16 pair rows [hi | lo] (include/omp355.h)
-ABI_VERSION = 21
+ABI_VERSION = 22
 STORE_PLAIN, STORE_KBLK, STORE_VBLK, STORE_ROWSTAT = 0, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 DEC_PT, DEC_POLY, DEC_REC = 0, 1, 2
@@ -70,7 +70,7 @@ class DecoderPlan(ctypes.Structure):
                 + [(n, c_void_p) for n in ('word_emb', 'pos_tab', 'emb_g', 'emb_b', 'fn_g', 'fn_b',
                                            'h0_w', 'h1_w', 'h2_w', 'h0_b', 'h1_b', 'h2_b')]
                 + [('kv_img_stride', c_int64)]
-                + [('key_mask', c_void_p), ('tiles', c_void_p), ('seq', c_void_p), ('seq_ld', c_int32),
+                + [('key_mask', c_void_p), ('key_len', c_void_p), ('tiles', c_void_p), ('seq', c_void_p), ('seq_ld', c_int32),
                    ('d_pos', c_void_p), ('probs', c_void_p), ('finished', c_void_p), ('lengths', c_void_p)]
                 + [(n, c_void_p) for n in ('x', 'x2', 'y', 'qkv', 'att', 'q', 'ffh', 'hh0', 'hh1',
                                            'partial', 'logits')]
@@ -102,7 +102,7 @@ _SIGS = {
     'omp_sine_posembed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'omp_dec_embed_ln': (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_void_p]),
     'omp_dec_self_attn_step': (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
-    'omp_dec_cross_attn_step': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+    'omp_dec_cross_attn_step': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                         c_int, c_void_p]),
     'omp_head_softmax_mask_argmax': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(SampleCfg), c_void_p,

@@ -531,10 +531,12 @@ struct CrossP {
   const void* K; const void* V;   // this layer's slabs
   int64_t img_stride;             // elements between images: nH * Mpad * 64 (K and V^T alike)
   const uint8_t* kmask;
+  const int32_t* klen;            // NULL, or keys per image [B] (ragged batches): image b's keys are slab positions 0 .. klen[b]-1
   const int32_t* groups;          // {row0, nrows (<= 16*QT), image}
   void* out; int64_t ldo;
   float* partial;
   int M, Mpad, nH, R, kpw;        // kpw: keys per wave, multiple of the key block
+  int slices;                     // key ranges per (image, head): kpw = round_up(ceil(M / slices), KB); with klen, per image
   int lo_off;                     // split-plane slabs only: > 0 = the output rows are split-bf16 pairs, lo plane lo_off columns after hi (ldo in bf16 elements)
 };
 
@@ -593,6 +595,20 @@ __device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
   for (int i = 0; i < 8; ++i) { hi[i] = (bf16_t)v[i]; lo[i] = (bf16_t)(v[i] - (float)hi[i]); }
 }
 
+// keys of this group's image and its per-range width.  klen == NULL: M and the launch's kpw, untouched.  Otherwise image b has klen[b]
+// keys (clamped to [1, M], so that a bad length can neither read past the slab nor leave the S = 1 store without a key) and its own
+// kpw_b = round_up(ceil(klen[b] / slices), KB) -- today's kpw when klen[b] == M, so the ranges and the summation order are the same.
+// Blocks at or beyond ceil(klen[b] / KB) are never loaded; a range that starts beyond klen[b] is empty (m = -inf, l = 0).
+template <int KB>
+__device__ __forceinline__ void image_keys(const CrossP& p, int img, int& M, int& kpw) {
+  M = p.M; kpw = p.kpw;
+  if (p.klen != nullptr) {
+    const int n = p.klen[img];
+    M = n < 1 ? 1 : (n > p.M ? p.M : n);
+    kpw = (((M + p.slices - 1) / p.slices + KB - 1) / KB) * KB;
+  }
+}
+
 // wait until at most `blocks` of this wave's most recently issued key blocks (IPB DMA instructions each) are
 // still in flight (the count must be an immediate; the switch is wave-uniform)
 template <int IPB>
@@ -624,9 +640,11 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
   const int row0 = p.groups[grp * 3], nrows = p.groups[grp * 3 + 1], img = p.groups[grp * 3 + 2];
   const int nqt = (nrows + 15) >> 4;
   const int S = gridDim.z, sp = blockIdx.z;
-  const int kbeg = (sp * NW + wave) * p.kpw;
-  int kend = kbeg + p.kpw;
-  if (kend > p.M) kend = p.M;
+  int Mi, kpw;
+  image_keys<KB>(p, img, Mi, kpw);
+  const int kbeg = (sp * NW + wave) * kpw;
+  int kend = kbeg + kpw;
+  if (kend > Mi) kend = Mi;
   const int nblk = kbeg < kend ? (kend - kbeg + KB - 1) / KB : 0;
 
   // K / V^T fragment addresses of this lane inside the (image, head) slabs
@@ -872,9 +890,11 @@ __global__ __launch_bounds__(256) void dec_cross_attn_q4_kernel(CrossP p) {
   const int grp = blockIdx.x, h = blockIdx.y, sp = blockIdx.z, S = gridDim.z;
   const int row0 = p.groups[grp * 3], nrows = p.groups[grp * 3 + 1], img = p.groups[grp * 3 + 2];
   const bool active = wave * 16 < nrows;          // wave-uniform: this wave's query tile exists
-  const int kbeg = sp * p.kpw;                    // kpw: keys per workgroup split, multiple of KB
-  int kend = kbeg + p.kpw;
-  if (kend > p.M) kend = p.M;
+  int Mi, kpw;                                    // kpw: keys per workgroup split, multiple of KB
+  image_keys<KB>(p, img, Mi, kpw);
+  const int kbeg = sp * kpw;
+  int kend = kbeg + kpw;
+  if (kend > Mi) kend = Mi;
   const int nblk = kbeg < kend ? (kend - kbeg + KB - 1) / KB : 0;
   const int nchunk = (nblk + CH - 1) / CH;
   auto tsw = [](int q) -> int { return (0x1320 >> (q * 4)) & 3; };   // t = {0, 2, 3, 1}
@@ -1439,6 +1459,7 @@ int launch_cross(CrossP cp, int n_groups, int dtype, int S, int qt, hipStream_t 
   const bool q4 = cx.cross_q4 != 0 && qt == 4;   // waves own query tiles, not key slices (bf16 and fp32 slabs alike)
   const int slices = q4 ? S : S * 4;
   cp.kpw = (((cp.M + slices - 1) / slices + KB - 1) / KB) * KB;
+  cp.slices = slices;
   const bool prof = omp_prof_active(OMP_PROF_CROSS) && !g_capturing;
   int prof_slot = -1;
   if (prof) {
@@ -1563,9 +1584,9 @@ extern "C" int omp_dec_self_attn_step(const void* qkv, void* kcache, void* vcach
 }
 
 extern "C" int omp_dec_cross_attn_step(const void* q, int64_t ldq, const void* K, const void* Vt, int64_t img_stride,
-                                       int Mpad, const uint8_t* key_mask, const int32_t* groups, int n_groups,
-                                       int q_tiles, int R, float* partial, void* out, int64_t ldo, int dtype, int M,
-                                       int nH, int n_split, omp_stream_t s) {
+                                       int Mpad, const uint8_t* key_mask, const int32_t* key_len, const int32_t* groups,
+                                       int n_groups, int q_tiles, int R, float* partial, void* out, int64_t ldo, int dtype,
+                                       int M, int nH, int n_split, omp_stream_t s) {
   OMP_CHECK_ARG(q && K && Vt && groups && out, "omp_dec_cross_attn_step: null pointer");
   OMP_CHECK_ARG(R > 0, "omp_dec_cross_attn_step: bad R");
   OMP_CHECK_ARG(dtype == OMP_F32 || dtype == OMP_BF16 || dtype == OMP_BF16X2, "omp_dec_cross_attn_step: bad dtype");
@@ -1573,7 +1594,7 @@ extern "C" int omp_dec_cross_attn_step(const void* q, int64_t ldq, const void* K
   OMP_CHECK_ARG(dtype != OMP_BF16X2 || (ldq % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)out % 16) == 0),
                 "omp_dec_cross_attn_step: split-plane slabs take 16-byte aligned fp32 q / out rows");
   CrossP cp;
-  cp.q = q; cp.ldq = ldq; cp.K = K; cp.V = Vt; cp.img_stride = img_stride; cp.kmask = key_mask; cp.groups = groups;
+  cp.q = q; cp.ldq = ldq; cp.K = K; cp.V = Vt; cp.img_stride = img_stride; cp.kmask = key_mask; cp.klen = key_len; cp.groups = groups;
   cp.out = out; cp.ldo = ldo; cp.partial = partial; cp.M = M; cp.Mpad = Mpad; cp.nH = nH; cp.R = R; cp.kpw = 0; cp.lo_off = 0;
   return launch_cross(cp, n_groups, dtype, n_split, q_tiles, (hipStream_t)s);
 }
@@ -1674,7 +1695,7 @@ int step_launch_x3(const omp_decoder_plan* P, bool do_head, hipStream_t st) {
   const int S2 = OMP_BF16X2, F = OMP_F32;
   CrossP cp;
   cp.q = P->q; cp.ldq = d; cp.img_stride = P->kv_img_stride; cp.Mpad = P->Mpad;
-  cp.kmask = P->key_mask; cp.groups = P->tiles; cp.out = P->att; cp.ldo = d;
+  cp.kmask = P->key_mask; cp.klen = P->key_len; cp.groups = P->tiles; cp.out = P->att; cp.ldo = d;
   cp.partial = P->partial; cp.M = P->M; cp.nH = P->n_heads; cp.R = R; cp.kpw = 0; cp.lo_off = 0;
   RUN(omp_dec_embed_ln(P->seq, P->seq_ld, P->d_pos, P->word_emb, P->pos_tab, P->emb_g, P->emb_b, P->x, nullptr, F, R, d, P->eps, st));
   void* ys = P->y;       // [R, 2d] bf16 split pairs (the bytes of the fp32 [R, d] buffer)
@@ -1781,7 +1802,7 @@ struct RowsStep {
     a.qkv = P->qkv; a.q = P->q; a.logits = P->logits; a.vocab = P->vocab; a.h0_b = P->h0_b; a.h1_b = P->h1_b; a.h2_b = P->h2_b;
     a.xcd_mask = P->rows_xcd_mask;
     cp.q = P->q; cp.ldq = d; cp.img_stride = P->kv_img_stride; cp.Mpad = P->Mpad;
-    cp.kmask = P->key_mask; cp.groups = P->tiles; cp.partial = P->partial; cp.M = P->M; cp.nH = P->n_heads; cp.R = R; cp.kpw = 0;
+    cp.kmask = P->key_mask; cp.klen = P->key_len; cp.groups = P->tiles; cp.partial = P->partial; cp.M = P->M; cp.nH = P->n_heads; cp.R = R; cp.kpw = 0;
     if (x3 && P->kv_split) { cp.out = P->ffh; cp.ldo = 2 * (int64_t)d; cp.lo_off = d; }   // the split-plane kernels write the chains' pair rows themselves
     else { cp.out = P->att; cp.ldo = d; cp.lo_off = 0; }
   }
@@ -1872,7 +1893,7 @@ int step_launch(const omp_decoder_plan* P, bool do_head, hipStream_t st) {
                          P->pre_norm ? nullptr : P->y, T, R, d, P->eps, st));
   CrossP cp;
   cp.q = P->q; cp.ldq = d; cp.img_stride = P->kv_img_stride; cp.Mpad = P->Mpad;
-  cp.kmask = P->key_mask; cp.groups = P->tiles; cp.out = P->att; cp.ldo = d;
+  cp.kmask = P->key_mask; cp.klen = P->key_len; cp.groups = P->tiles; cp.out = P->att; cp.ldo = d;
   cp.partial = P->partial; cp.M = P->M; cp.nH = P->n_heads; cp.R = R; cp.kpw = 0; cp.lo_off = 0;
   const int TC = P->kv_split ? OMP_BF16X2 : T;   // slab format the cross-attention kernels read (split planes: fp32 q / out)
   // Phases between the fused few-row kernels (<= 63 rows) and the full chains (rows_fused): when the caller bound layers[].rows_mid, the three

@@ -2,7 +2,9 @@
 (OCR/OmniParser/engine/val.py:11-100), plus a `predict()` convenience API.
 
   * prompts are built exactly like val.py:25-33;
-  * B images per call (the reference asserts 1);
+  * B images per call (the reference asserts 1).  Images of different sizes are padded to the largest and masked (the
+    default), or with `ragged=True` each is encoded and decoded at its own size -- the answers of one call per image
+    (OmniParser.infer);
   * `validate` is image-sharded: under torch.distributed every rank decodes a contiguous shard of the dataloader's
     items (utils/dist.py::shard_range), the decoded token tensors meet in ONE all-gather per tensor at the end
     (pack_results / all_gather_results: RCCL over xGMI on MI355X, gloo in the CPU tests) and rank 0 alone writes the
@@ -67,15 +69,33 @@ def _as_nested(images):
     return nested_tensor_from_tensor_list(list(images))
 
 
+def _ragged_inputs(images, dev):
+    """ragged calls: the unpadded images of whatever the caller has (a list of (3,H,W) tensors stays a list; a padded batch keeps its
+    mask, from which OmniParser.infer reads every image's extent) -> (img, mask, [(h, w)] per image)"""
+    from ..model.omniparser import mask_extents
+    if isinstance(images, (list, tuple)):
+        imgs = [torch.as_tensor(i).to(dev) for i in images]
+        return imgs, None, [(int(i.shape[1]), int(i.shape[2])) for i in imgs]
+    nt = _as_nested(images).to(dev)
+    return nt.tensors, nt.mask, mask_extents(nt.mask)
+
+
 @torch.no_grad()
-def predict_raw(model, images, args, orig_sizes=None):
-    """-> (per-image raw model outputs exactly as the reference's forward returns them, NestedTensor on the device)."""
-    nt = _as_nested(images)
+def predict_raw(model, images, args, orig_sizes=None, ragged=False):
+    """-> (per-image raw model outputs exactly as the reference's forward returns them, NestedTensor on the device).
+    ragged=True: every image is decoded at its own size, no padding (OmniParser.infer(ragged=True)); the second value is then the
+    list of (h, w) per image, and the KIE default orig_size is each image's own size."""
     dev = next(model.parameters()).device
+    seqs = build_prompts(args)
+    if ragged:
+        img, mask, sizes = _ragged_inputs(images, dev)
+        if args.infer_vie:
+            seqs.append([torch.as_tensor(s) for s in (orig_sizes if orig_sizes is not None else sizes)])
+        return model.infer(img, mask, seqs, ragged=True), sizes
+    nt = _as_nested(images)
     B = nt.tensors.shape[0]
     has_padding = bool(nt.mask.any())
     nt = nt.to(dev)
-    seqs = build_prompts(args)
     if args.infer_vie:
         if orig_sizes is None:
             orig_sizes = [(int(nt.tensors.shape[2]), int(nt.tensors.shape[3]))] * B
@@ -84,12 +104,15 @@ def predict_raw(model, images, args, orig_sizes=None):
 
 
 @torch.no_grad()
-def predict(model, images, args, targets=None, orig_sizes=None):
+def predict(model, images, args, targets=None, orig_sizes=None, ragged=False):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
-    Returns one entry per image: list of records (text spotting), list of tuples (KIE) or []."""
+    Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
+    ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
+    others in the call.  ragged=True: every image is decoded exactly as if it had been submitted alone; without targets its
+    orig_size is its own (h, w), not the padded batch's."""
     if orig_sizes is None and targets is not None and args.infer_vie:
         orig_sizes = [t['orig_size'] for t in targets]
-    raw, nt = predict_raw(model, images, args, orig_sizes)
+    raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged)
     if args.infer_vie:
         return [r if r is not None else [] for r in raw]
     out = []
@@ -98,17 +121,18 @@ def predict(model, images, args, targets=None, orig_sizes=None):
             out.append([])
             continue
         tgt = (targets[b] if targets is not None else
-               {'file_name': str(b), 'orig_size': (nt.tensors.shape[2], nt.tensors.shape[3])})
+               {'file_name': str(b), 'orig_size': nt[b] if ragged else (nt.tensors.shape[2], nt.tensors.shape[3])})
         seq_cpu = [t[0].cpu() for t in r[0]]
         out.append(decode_pred_seq(seq_cpu, r[1][0].cpu(), tgt, args))
     return out
 
 
 @torch.no_grad()
-def predict_images(model, images_u8, args, file_names=None, preprocessor=None):
+def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
+    ragged=True: the preprocessed images are decoded at their own sizes (predict), not padded to the largest of the call.
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
     dev = next(model.parameters()).device
@@ -118,7 +142,7 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None):
     nt, _ = preprocessor(imgs)
     targets = [{'file_name': (file_names[b] if file_names is not None else str(b)),
                 'orig_size': (int(im.shape[0]), int(im.shape[1]))} for b, im in enumerate(imgs)]
-    return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets]), preprocessor
+    return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged), preprocessor
 
 
 def _meta(t):
@@ -213,16 +237,18 @@ def _rank_items(dataloader, rank, ws, sharded):
 
 
 @torch.no_grad()
-def validate(model, dataloader, epoch, args, batch_size=1):
+def validate(model, dataloader, epoch, args, batch_size=1, ragged=False):
     """Drop-in for engine.validate (val.py:11-68), image-sharded over the ranks of torch.distributed.
 
     dataloader yields (samples, targets) as the reference's does (samples: NestedTensor of 1 or more images, targets:
     list of dicts with file_name / orig_size / dataset_name).  Rank r decodes items [lo, hi) = shard_range(len, r, W)
     -- a loader that is already rank-sharded (DistributedSampler: `args.dataloader_is_sharded`) is consumed whole --
-    `batch_size` consecutive items are merged into one engine call (different sizes are padded and masked exactly as the
-    reference's collate would), decoded token tensors are packed to fixed size and all-gathered ONCE at the end, and
+    `batch_size` consecutive items are merged into one engine call, decoded token tensors are packed to fixed size and all-gathered ONCE at the end, and
     rank 0 formats and writes <output_folder>/results/epXXX/<dataset>.json (text spotting) or one <file_name>.json per
     image (KIE).  Returns the records on rank 0 (a list; per-image lists for KIE) and [] elsewhere.
+    Images of different sizes in one engine call: ragged=False pads them to the largest and masks the padding, as the reference's
+    collate would for a batch it never runs (val.py:22 asserts batch 1) -- an image's tokens may then depend on the others in its call.
+    ragged=True hands the model the unpadded images (OmniParser.infer(ragged=True)): every image is decoded as at batch_size=1.
     args.eos_pred_counts (optional: one predicted instance count per dataloader item) switches the contiguous shards for plan_eos_balance's:
     cost-balanced across ranks, homogeneous inside an engine call; the output is the same, in dataset order."""
     model.eval()
@@ -254,7 +280,7 @@ def validate(model, dataloader, epoch, args, batch_size=1):
     def flush():
         if not pend_imgs:
             return
-        raw, _ = predict_raw(model, list(pend_imgs), args, [t['orig_size'] for t in pend_tg] if args.infer_vie else None)
+        raw, _ = predict_raw(model, list(pend_imgs), args, [t['orig_size'] for t in pend_tg] if args.infer_vie else None, ragged=ragged)
         local_raw.extend(raw)
         for t, key in zip(pend_tg, pend_key):
             m = _meta(t)

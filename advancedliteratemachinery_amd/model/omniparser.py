@@ -5,7 +5,9 @@ OCR/OmniParser/model/omniparser.py:7-32 (eval mode), with the computation execut
 libomp355 (hand-written gfx950 kernels).  Additions over the reference:
   * batches of B > 1 images (the reference asserts B == 1, engine/val.py:22): every image is
     decoded exactly as if it had been submitted alone; `forward` then returns a list of B results;
-  * `forced_instances`: fixed-length decoding for throughput measurement with random weights.
+  * `forced_instances`: fixed-length decoding for throughput measurement with random weights;
+  * `infer(..., ragged=True)`: images of different sizes in one call, each encoded and decoded at its own size (no
+    padding anywhere) -- the reference's batch-1 answers with a batch's decode throughput.
 
 Return value per image (reference transformer.py:240-246,286):
   text spotting : ([pt (1,2N), poly (1,32N), rec (1,N,rec_length)] int64, [probs (N,rec_length)])
@@ -39,6 +41,36 @@ def _image_sizes(sizes, B):
     if t.shape[0] == 1 and B > 1:
         t = t.expand(B, 2)
     return t.cpu()
+
+
+def mask_extents(mask):
+    """(h, w) of every image of a padded batch, read off its padding mask (True = padding): the image fills the top-left h x w
+    corner, as nested_tensor_from_tensor_list puts it.  A mask of another shape is refused rather than guessed at."""
+    m = mask.bool()
+    B, H, W = m.shape
+    h, w = (~m[:, :, 0]).sum(1), (~m[:, 0, :]).sum(1)
+    ys, xs = torch.arange(H, device=m.device), torch.arange(W, device=m.device)
+    rect = (ys[None, :, None] >= h[:, None, None]) | (xs[None, None, :] >= w[:, None, None])
+    if not torch.equal(rect, m) or bool((h == 0).any()) or bool((w == 0).any()):
+        raise ValueError('ragged: every image of a padded batch must fill the top-left corner of its mask (True = padding)')
+    return list(zip(h.tolist(), w.tolist()))
+
+
+def bucket_by_size(sizes):
+    """[(h, w)] per image -> [((h, w), [image indices])]: one encoder pass per distinct size, in order of first appearance"""
+    groups = {}
+    for i, hw in enumerate(sizes):
+        groups.setdefault(tuple(int(v) for v in hw), []).append(i)
+    return list(groups.items())
+
+
+def ragged_layout(keys, align=64):
+    """memory keys M_b per image -> (Mmax, key_len, row0): image b's memory rows start at row0[b] = b * Mmax, with
+    Mmax = round_up(max M_b, align) (a multiple of 64 keeps omp_kv_project_rows' bf16 path), and it attends over its first
+    key_len[b] = M_b keys only (Decoder.project_memory)."""
+    key_len = [int(n) for n in keys]
+    Mmax = (max(key_len) + align - 1) // align * align
+    return Mmax, key_len, [b * Mmax for b in range(len(key_len))]
 
 
 class OmniParser(nn.Module):
@@ -126,27 +158,50 @@ class OmniParser(nn.Module):
 
     # -- batched inference ------------------------------------------------------------------------
     @torch.no_grad()
-    def infer(self, img, mask, sequence, forced_instances=None, has_padding=None, lane=None, packed=None):
+    def infer(self, img, mask, sequence, forced_instances=None, has_padding=None, lane=None, packed=None, ragged=False):
         """lane: a pipeline Lane (engine/pipeline.py) -- private decoder state + side streams, so several
         batches can be in flight on different HIP streams; None = the model's own state.
         packed = N (text spotting only): return (ids int32 [B, N, 34 + rec_length], probs [B, N, rec_length], n_inst [B]) device
         tensors -- the all-gather payload of utils/dist.py -- packed by ONE kernel from the decoders' buffers instead of the
-        per-image result lists (no per-image host work or device copies)."""
+        per-image result lists (no per-image host work or device copies).
+        ragged=True: every image is encoded and decoded at its OWN size, as if it had been submitted alone -- `img` is a list of
+        [3, h_b, w_b] device tensors (mask None), or a padded batch whose mask gives each image's extent (mask_extents).  Images
+        of one size share an encoder pass; the decoders run once for all, each image's cross-attention reading its own M_b keys
+        and no others (Decoder.project_memory key_len).  One size only: the padding-free path below, unchanged.  packed= is
+        padded-only."""
         enc, dec = self.engine()
         side = None
         if lane is not None:
             dec, side = lane.decoder(dec), (lane.side if lane.side is not None else False)   # False: no side streams at all
+        groups = None
+        if ragged:
+            imgs = self._ragged_images(img, mask)
+            groups = bucket_by_size([tuple(i.shape[1:]) for i in imgs])
+            if len(groups) == 1:   # nothing ragged about it: the ordinary call on the unpadded images
+                (h, w), _ = groups[0]
+                if not torch.is_tensor(img) or tuple(img.shape[2:]) != (h, w):
+                    img = torch.stack(imgs)
+                mask = torch.zeros(img.shape[0], h, w, dtype=torch.bool, device=img.device)
+                has_padding, groups = False, None
+            elif packed is not None:
+                raise ValueError('infer: packed= results are produced for padded batches only; call with ragged=False')
         a = self.args
-        dev = img.device
-        B = img.shape[0]
+        dev = imgs[0].device if groups is not None else img.device
+        B = len(imgs) if groups is not None else img.shape[0]
         with torch.cuda.device(dev):
-            img = img.float().contiguous()
-            if has_padding is None:
-                has_padding = bool(mask.any())
-            self._mark('start')
-            e = self._encode_chunked(enc, img, mask, no_padding=not has_padding)
-            self._mark('encode')
-            kv = dec.project_memory(e['memory'], e['mem_pos'], B, e['M'], e['key_mask'] if has_padding else None)
+            if groups is not None:
+                self._mark('start')
+                memory, mem_pos, Mmax, key_len = self._encode_ragged(enc, imgs, groups)
+                self._mark('encode')
+                kv = dec.project_memory(memory, mem_pos, B, Mmax, None, key_len=key_len)
+            else:
+                img = img.float().contiguous()
+                if has_padding is None:
+                    has_padding = bool(mask.any())
+                self._mark('start')
+                e = self._encode_chunked(enc, img, mask, no_padding=not has_padding)
+                self._mark('encode')
+                kv = dec.project_memory(e['memory'], e['mem_pos'], B, e['M'], e['key_mask'] if has_padding else None)
             prompt = [int(t) for t in sequence[0].reshape(-1).tolist()]
             poly_sos = int(sequence[1].reshape(-1)[0])
             rec_sos = int(sequence[2].reshape(-1)[0])
@@ -196,6 +251,44 @@ class OmniParser(nn.Module):
         out['pos'] = torch.cat(pos, 0)   # small (diagnostics / parity tests only: the decoders read mem_pos)
         out['key_mask'] = torch.cat(km, 0)
         return out
+
+    @staticmethod
+    def _ragged_images(img, mask):
+        """the images of a ragged call, unpadded: a list / tuple of [3, h, w] tensors as given, or the extents of a padded batch"""
+        if torch.is_tensor(img):
+            if img.dim() != 4:
+                raise ValueError('ragged: a padded batch is [B, 3, H, W] (got %s)' % (tuple(img.shape),))
+            if mask is None:
+                return list(img)
+            return [im[:, :h, :w] for im, (h, w) in zip(img, mask_extents(mask))]
+        imgs = list(img)
+        if not imgs or any(not torch.is_tensor(i) or i.dim() != 3 for i in imgs):
+            raise ValueError('ragged: give a list of [3, h, w] image tensors or a padded batch and its mask')
+        if len(set(i.device for i in imgs)) != 1:
+            raise ValueError('ragged: all images of a call live on one device')
+        return imgs
+
+    def _encode_ragged(self, enc, imgs, groups):
+        """One encoder pass per size group (chunked as _encode_chunked does); every image's memory and mem_pos rows are placed at
+        row0[b] = b * Mmax of the call's memory tensors, the rows beyond its M_b stay zero (finite: they are projected into the slabs).
+        -> (memory, mem_pos, Mmax, key_len)"""
+        B, dev = len(imgs), imgs[0].device
+        parts, keys = [], [0] * B
+        for (h, w), idx in groups:
+            x = torch.stack([imgs[i] for i in idx]).float().contiguous()
+            e = self._encode_chunked(enc, x, torch.zeros(len(idx), h, w, dtype=torch.bool, device=dev), no_padding=True)
+            parts.append((idx, e['M'], e['memory'], e['mem_pos']))
+            for i in idx:
+                keys[i] = e['M']
+        Mmax, key_len, row0 = ragged_layout(keys)
+        mem0 = parts[0][2]
+        memory = torch.zeros((B * Mmax, mem0.shape[1]), dtype=mem0.dtype, device=dev)
+        mem_pos = torch.zeros_like(memory)
+        for idx, M, mem, mp in parts:
+            rows = (torch.tensor([row0[i] for i in idx])[:, None] + torch.arange(M)[None, :]).reshape(-1).to(dev)
+            memory.index_copy_(0, rows, mem)
+            mem_pos.index_copy_(0, rows, mp)
+        return memory, mem_pos, Mmax, key_len
 
     def _decode(self, dec, kv, prompt, poly_sos, rec_sos, sequence, forced_instances, B, dev, side, packed=None):
         """point decoder -> polygon || recognition decoders (or the KIE walk) on the current stream"""

@@ -257,14 +257,21 @@ class Decoder(object):
         return self._x3_cache[kind]
 
     # -- memory K/V: once per batch ---------------------------------------------------------------
-    def project_memory(self, memory, mem_pos, B, M, key_mask):
+    def project_memory(self, memory, mem_pos, B, M, key_mask, key_len=None):
         """Cross-attention memory of all (decoder, layer) pairs, written by the GEMM epilogues straight into
         the head-blocked slabs the step kernel streams (DESIGN.md "cross-attention memory layout"):
           K   = (memory+pos) Wk^T + bk  ->  [NL][B][nH][Mpad][64]
           V^T = (memory Wv^T + bv)^T    ->  [NL][B][nH][Mpad/KB][64][KB]
-        The padded tail (keys >= M) is zero from allocation and never written."""
+        The padded tail (keys >= M) is zero from allocation and never written.
+        key_len (ragged batches, OmniParser.infer(ragged=True)): image b's M_b = key_len[b] keys are memory rows b * M ..
+        b * M + M_b - 1; rows M_b .. M - 1 must be finite (they are projected, and the last loaded key block of an image
+        reaches into them).  The cross-attention kernels read no key beyond M_b (include/omp355.h omp_dec_cross_attn_step)."""
         KB = 16 if (self.dtype == torch.float32 and not self.kv_split) else 32
         Mpad = _round_up(M, KB)
+        if key_len is not None:
+            key_len = [int(n) for n in key_len]
+            if len(key_len) != B or min(key_len) < 1 or max(key_len) > M:
+                raise ValueError('project_memory: key_len must hold B = %d counts in [1, %d], got %s' % (B, M, key_len))
         key = (B, M)
         if key not in self._kv:
             while len(self._kv) >= MAX_KV_ENTRIES:
@@ -275,13 +282,17 @@ class Decoder(object):
             else:
                 slabs = (torch.zeros(self.NL, B, self.nH, Mpad, 64, dtype=self.dtype, device=self.device),
                          torch.zeros(self.NL, B, self.nH, Mpad // KB, 64, KB, dtype=self.dtype, device=self.device))
-            self._kv[key] = slabs + (torch.zeros(B, M, dtype=torch.uint8, device=self.device),)
+            self._kv[key] = slabs + (torch.zeros(B, M, dtype=torch.uint8, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
         self._kv.move_to_end(key)
-        K_all, Vt_all, mask_buf = self._kv[key]
+        K_all, Vt_all, mask_buf, len_buf = self._kv[key]
         if key_mask is not None:
             # a STABLE buffer: the plan (and the graph captured from it) holds this pointer, not the caller's tensor
             mask_buf.copy_(key_mask.reshape(B, M))
             key_mask = mask_buf
+        if key_len is not None:
+            # the same for the key counts: a replayed graph reads this buffer, so every call rewrites it in stream order
+            len_buf.copy_(torch.tensor(key_len, dtype=torch.int32))
+            key_len = len_buf
         geom = (B, M, Mpad, self.nH, KB)
         if self.x3:
             d = self.d
@@ -290,7 +301,7 @@ class Decoder(object):
                      M=B * M, N=self.Wk_all.shape[0], K=3 * d)
             ops.gemm(self.Wv_all, ops.split_bf16(memory, triple=True), self.bv_all, out=Vt_all, out_dtype=od, store_mode=_lib.STORE_VBLK, kv=geom,
                      bias_along_m=True, a_wrap=2 * d, M=self.Wv_all.shape[0], N=B * M, K=3 * d)
-            return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask)
+            return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask, key_len=key_len)
         if self.kv_rows and self.dtype == torch.bfloat16 and self.d == 512 and self.nH == 8 and M % 64 == 0:
             # one row-owner launch per tensor (csrc/kv_rows.hip): 64 memory rows per workgroup, the weights of all slabs streamed; bit-identical slabs
             if self._kv_streams is None:
@@ -298,12 +309,12 @@ class Decoder(object):
             (sk, nk), (sv, nv) = self._kv_streams
             ops.kv_project_rows(mem_pos, sk, nk, self.bk_all, K_all, B, M, Mpad, self.NL, False)
             ops.kv_project_rows(memory, sv, nv, self.bv_all, Vt_all, B, M, Mpad, self.NL, True)
-            return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask)
+            return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask, key_len=key_len)
         ops.gemm(mem_pos, self.Wk_all, self.bk_all, out=K_all, store_mode=_lib.STORE_KBLK, kv=geom)
         # swapped operands: rows = value features, columns = memory tokens, so a lane owns 4 consecutive keys
         ops.gemm(self.Wv_all, memory, self.bv_all, out=Vt_all, store_mode=_lib.STORE_VBLK, kv=geom, bias_along_m=True,
                  M=self.Wv_all.shape[0], N=B * M, K=self.d)
-        return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask)
+        return dict(K=K_all, Vt=Vt_all, B=B, M=M, Mpad=Mpad, KB=KB, key_mask=key_mask, key_len=key_len)
 
     # -- plans --------------------------------------------------------------------------------------
     def _phase(self, kind, R, Lmax, seq_ld, n_split):
@@ -388,6 +399,7 @@ class Decoder(object):
                                                                  for i, (w, b) in enumerate(self.head[ph.kind])]
         P.kv_img_stride = img_stride * (2 if self.kv_split else 1)   # in slab elements: two bf16 planes per (key, dim)
         P.key_mask = kv['key_mask'].data_ptr() if kv['key_mask'] is not None else None
+        P.key_len = kv['key_len'].data_ptr() if kv.get('key_len') is not None else None
         P.tiles = ph.tiles.data_ptr()
         P.seq, P.seq_ld, P.d_pos, P.probs = ph.seq.data_ptr(), ph.seq_ld, ph.d_pos.data_ptr(), ph.probs.data_ptr()
         P.finished, P.lengths = ph.finished.data_ptr(), ph.lengths.data_ptr()
@@ -397,7 +409,7 @@ class Decoder(object):
         s.kind, s.num_bins, s.pt_eos, s.poly_eos, s.rec_eos = KIND_ID[ph.kind], a.num_bins, a.pt_eos_index, a.poly_eos_index, a.rec_eos_index
         s.vocab, s.vie_categories, s.infer_vie = self.V, a.vie_categories, 1 if infer_vie else 0
         s.suppress_eos, s.step0 = 1 if suppress_eos else 0, n_prompt
-        ph._keepalive = (kv['K'], kv['Vt'], kv['key_mask'])
+        ph._keepalive = (kv['K'], kv['Vt'], kv['key_mask'], kv.get('key_len'))
         return P
 
     def fork(self):

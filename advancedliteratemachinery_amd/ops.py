@@ -291,9 +291,12 @@ def dec_self_attn_step(qkv, kcache, vcache, out, d_pos, nH):
     _lib.check(rc, 'omp_dec_self_attn_step')
 
 
-def dec_cross_attn_step(q, K, Vt, img_stride, Mpad, key_mask, groups, n_groups, q_tiles, partial, out, M, nH, n_split):
+def dec_cross_attn_step(q, K, Vt, img_stride, Mpad, key_mask, groups, n_groups, q_tiles, partial, out, M, nH, n_split, key_len=None):
     """K / Vt in q's dtype: the bf16 / fp32 slabs; fp32 q with bf16 K / Vt: SPLIT-PLANE slabs (OMP_BF16X2: 32-key blocks of
-    [hi plane | lo plane], img_stride = nH * Mpad * 128 bf16 elements; fp32 out)."""
+    [hi plane | lo plane], img_stride = nH * Mpad * 128 bf16 elements; fp32 out).
+    key_len: None, or device int32 [B] with 1 <= key_len[b] <= M -- image b attends over its first key_len[b] keys only (ragged batches)."""
+    if key_len is not None and (key_len.dtype != torch.int32 or not key_len.is_contiguous()):
+        raise TypeError('dec_cross_attn_step: key_len is a contiguous int32 device tensor')
     R = q.shape[0]
     split = q.dtype == torch.float32 and K.dtype == torch.bfloat16
     if split and (Vt.dtype != torch.bfloat16 or out.dtype != torch.float32):
@@ -301,7 +304,7 @@ def dec_cross_attn_step(q, K, Vt, img_stride, Mpad, key_mask, groups, n_groups, 
     if not split and (K.dtype != q.dtype or Vt.dtype != q.dtype or out.dtype != q.dtype):
         raise TypeError('dec_cross_attn_step: q, K, V^T and out share one dtype (or fp32 q / out over split-plane bf16 slabs)')
     rc = _lib.lib().omp_dec_cross_attn_step(ptr(q), q.stride(0), ptr(K), ptr(Vt), img_stride, Mpad, ptr(key_mask),
-                                            ptr(groups), n_groups, q_tiles, R, ptr(partial), ptr(out), out.stride(0),
+                                            ptr(key_len), ptr(groups), n_groups, q_tiles, R, ptr(partial), ptr(out), out.stride(0),
                                             OMP_BF16X2 if split else dt(q), M, nH, n_split, stream())
     _lib.check(rc, 'omp_dec_cross_attn_step')
 

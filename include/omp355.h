@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OMP_ABI_VERSION 21
+#define OMP_ABI_VERSION 22
 #define OMP_MAX_DEC_LAYERS 8
 
 enum { OMP_OK = 0, OMP_ERR_LAUNCH = -5, OMP_ERR_INVALID = -22, OMP_ERR_UNSUPPORTED = -95 };
@@ -270,11 +270,16 @@ int omp_dec_self_attn_step(const void* qkv, void* kcache, void* vcache, void* ou
  * bf16 (K [image][head][Mpad/32][2][32][64], V^T [image][head][Mpad/32][2][64][32], img_stride = nH*Mpad*128 bf16 elements; the
  * bytes of the fp32 slabs, written by omp_gemm_bias_act with out_dtype OMP_BF16X2 and a blocked store mode), q and out are fp32
  * rows; scores and values run as three bf16 matrix-core products each, i.e. fp32-grade results at the HBM rate.
+ * key_mask: NULL or uint8 [B][M], nonzero = padded key (masked).  key_len (ABI 22, ragged batches): NULL, or device int32 [B] with
+ * 1 <= key_len[b] <= M: image b's keys are slab positions 0 .. key_len[b]-1 (same slab layout and img_stride); no 32-/16-key block at
+ * or beyond ceil(key_len[b] / KB) is loaded, and each image's keys are cut like M keys would be, with key_len[b] in place of M
+ * (key_len[b] == M: the same ranges and bits as key_len = NULL).  key_mask, if also given, applies inside key_len.  Slab rows
+ * beyond key_len[b] are never read as keys but must not be NaN where a loaded block covers them (dead keys enter P.V with P = 0).
  * Replaces multihead_attn of transformer.py:416-420/:442-446 with memory.repeat (transformer.py:88-96). */
 int omp_dec_cross_attn_step(const void* q, int64_t ldq, const void* K, const void* Vt, int64_t img_stride,
-                            int Mpad, const uint8_t* key_mask, const int32_t* groups, int n_groups,
-                            int q_tiles, int R, float* partial, void* out, int64_t ldo, int dtype, int M,
-                            int nH, int n_split, omp_stream_t s);
+                            int Mpad, const uint8_t* key_mask, const int32_t* key_len, const int32_t* groups,
+                            int n_groups, int q_tiles, int R, float* partial, void* out, int64_t ldo, int dtype,
+                            int M, int nH, int n_split, omp_stream_t s);
 
 /* Greedy sampling of one step from logits [R, ld] fp32: softmax over the support, candidate
  * filtering, argmax, probability; appends the token at seq[r, *d_pos + 1], the probability at
@@ -365,7 +370,9 @@ typedef struct {
   const void *h0_w, *h1_w, *h2_w;
   const float *h0_b, *h1_b, *h2_b;
   int64_t kv_img_stride;
-  const uint8_t* key_mask;
+  const uint8_t* key_mask;     /* NULL or uint8 [B][M], nonzero = padded key; see omp_dec_cross_attn_step */
+  const int32_t* key_len;      /* NULL or device int32 [B], 1 <= key_len[b] <= M: ragged batches, see omp_dec_cross_attn_step (ABI 22).
+                                  Read by every step, so a graph_slot replay sees the buffer's contents at replay time */
   const int32_t* tiles;
   /* state */
   int32_t* seq;
