@@ -9,7 +9,8 @@
 //   * the coefficient tables (triangle filter widened by the down-scale factor, normalised in double, quantised
 //     to 22 fractional bits) are computed on the host exactly as Resample.c does and passed in;
 //   * horizontal pass first, its result ROUNDED TO uint8 (Pillow materialises a uint8 temporary), then the
-//     vertical pass; a thread recomputes the few horizontally-filtered pixels of its column footprint instead of
+//     vertical pass (the other way round where Image.resize itself swaps them: a source more than 100 times as high
+//     as wide that gets lower); a thread recomputes the few horizontally-filtered pixels of its column footprint instead of
 //     round-tripping a temporary image through HBM;
 //   * ToTensor/Normalize are a 3 x 256 float table built on the host with the reference's own float32 operations
 //     ((p / 255 - mean) / std), so no device rounding mode enters the result.
@@ -23,7 +24,8 @@ struct PreP {
   const int32_t* xb; const int32_t* kx; int ksx;   // [ow][2] (first, count), [ow][ksx]
   const int32_t* yb; const int32_t* ky; int ksy;   // [oh][2], [oh][ksy]
   int need_h, need_v;
-  const float* lut;                        // [3][256]
+  int vfirst;                              // vertical pass first (Pillow's Image.resize on a source more than 100 times as high as wide)
+  const float* lut;                       // [3][256]
   float* dst; int64_t plane;               // this image's [3][Hd][Wd] slice, plane = Hd * Wd
   uint8_t* mask;                           // [Hd][Wd] or nullptr
   int out_h, out_w, Hd, Wd;
@@ -53,6 +55,26 @@ __global__ __launch_bounds__(256) void resize_norm_pad_kernel(PreP p) {
   const int half = 1 << (PRE_BITS - 1);
   int v0 = half, v1 = half, v2 = half;
   int h0 = 0, h1 = 0, h2 = 0;
+  if (p.vfirst) {
+    // the same two passes in the other order: each column of the footprint is filtered vertically and rounded to uint8, then combined
+    int a0 = half, a1 = half, a2 = half;
+    for (int t = 0; t < nx; ++t) {
+      const uint8_t* col = p.src + (int64_t)y0 * p.src_pitch + (int64_t)(x0 + t) * 3;
+      int c0 = half, c1 = half, c2 = half;
+      for (int r = 0; r < ny; ++r) {
+        const int k = ky[r];
+        c0 += (int)col[0] * k; c1 += (int)col[1] * k; c2 += (int)col[2] * k;
+        col += p.src_pitch;
+      }
+      const int k = kx[t];
+      a0 += clip8(c0) * k; a1 += clip8(c1) * k; a2 += clip8(c2) * k;
+    }
+    p.dst[o] = p.lut[clip8(a0)];
+    p.dst[p.plane + o] = p.lut[256 + clip8(a1)];
+    p.dst[2 * p.plane + o] = p.lut[512 + clip8(a2)];
+    if (p.mask != nullptr) p.mask[o] = 0;
+    return;
+  }
   for (int r = 0; r < ny; ++r) {
     const uint8_t* row = p.src + (int64_t)(y0 + r) * p.src_pitch + (int64_t)x0 * 3;
     if (p.need_h) {
@@ -90,6 +112,9 @@ extern "C" int omp_resize_normalize_pad(const uint8_t* src, int64_t src_pitch, i
   PreP p;
   p.src = src; p.src_pitch = src_pitch; p.in_h = in_h; p.in_w = in_w;
   p.need_h = out_w != in_w; p.need_v = out_h != in_h;
+  // Image.resize runs the vertical pass first on an image more than 100 times as high as wide that gets lower; the passes round to
+  // uint8 and clip in between, so the order is part of the result
+  p.vfirst = p.need_h && p.need_v && (int64_t)in_h > (int64_t)in_w * 100 && out_h < in_h;
   OMP_CHECK_ARG(!p.need_h || (xbounds && xcoef && ksx > 0), "omp_resize_normalize_pad: width changes but no x coefficients");
   OMP_CHECK_ARG(!p.need_v || (ybounds && ycoef && ksy > 0), "omp_resize_normalize_pad: height changes but no y coefficients");
   p.xb = xbounds; p.kx = xcoef; p.ksx = ksx; p.yb = ybounds; p.ky = ycoef; p.ksy = ksy;

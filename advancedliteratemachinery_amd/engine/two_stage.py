@@ -8,13 +8,15 @@ path derives from a polygon, transformer.py:186-196: min / max over the points),
 way MGP-STR's own evaluation does (OCR/MGP-STR/dataset.py:462: `image.resize((128, 32), Image.BICUBIC)` + ToTensor;
 test_final.py:145-240: greedy ids, max-softmax confidences cumprod-ed to the first EOS, the most confident of the
 char / BPE / WordPiece heads wins).  Everything between the uint8 image and the token ids runs on the MI355X: no crop
-ever visits the host.
+ever visits the host.  crop='polygon' replaces the bounding box by the word rectified along its polygon
+(utils/word_crops.py): rotated, vertical and curved words arrive upright and tight.
 """
 import math
 
 import torch
 
 from ..utils.preprocess import CropResizer
+from ..utils.word_crops import PolygonCropper, polygon_strip_size
 from .inference import predict_images
 
 
@@ -31,39 +33,50 @@ def polygon_box(polys, width, height):
 
 
 @torch.no_grad()
-def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512):
-    """boxes: (image index, x0, y0, x1, y1).  -> list of MGPSTR.recognize results (one dict per box)."""
-    if not boxes:
+def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=None):
+    """boxes: (image index, x0, y0, x1, y1).  -> list of MGPSTR.recognize results (one dict per box).
+    polys: (image index, 16 x 2 points) per crop instead of boxes (boxes is then ignored): the crops are rectified along
+    their polygons (utils/word_crops.py: PolygonCropper), and `resizer` is a PolygonCropper."""
+    crops = boxes if polys is None else polys
+    if not crops:
         return [], resizer
     dev = images_u8[0].device
     if resizer is None:
         c = mgp_model.cfg
-        resizer = CropResizer(dev, c['img'][0], c['img'][1])
+        resizer = (CropResizer if polys is None else PolygonCropper)(dev, c['img'][0], c['img'][1])
     out = []
-    for i in range(0, len(boxes), chunk):
-        batch = resizer(images_u8, boxes[i:i + chunk])
+    for i in range(0, len(crops), chunk):
+        batch = resizer(images_u8, crops[i:i + chunk])
         out.extend(mgp_model.recognize(batch))
     return out, resizer
 
 
 @torch.no_grad()
-def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None):
+def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
     the three heads (the BPE / WordPiece STRINGS need the GPT-2 / BERT vocabulary files, which are not in the
-    reference tree).  Returns (results, preprocessor, resizer) so the cached tables can be reused."""
+    reference tree).  crop='box' reads the bounding box of each polygon; crop='polygon' reads the word rectified along
+    its polygon (rotated, vertical and curved text arrives upright and tight; `resizer` is then a PolygonCropper) and the
+    records gain `crop`: 'polygon' and `strip`: (sh, sw), the rectified word's own size.  `ragged` goes to predict_images.
+    Returns (results, preprocessor, resizer) so the cached tables can be reused."""
+    if crop not in ('box', 'polygon'):
+        raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
-    records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor)
-    boxes, owner = [], []
+    records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor, ragged=ragged)
+    boxes, polys, owner = [], [], []
     for b, recs in enumerate(records):
         h, w = int(imgs[b].shape[0]), int(imgs[b].shape[1])
         for r in recs:
             r['box'] = polygon_box(r['polys'], w, h)
             boxes.append((b,) + r['box'])
+            if crop == 'polygon':
+                r['crop'], r['strip'] = 'polygon', polygon_strip_size(r['polys'])
+                polys.append((b, r['polys']))
             owner.append(r)
-    reads, resizer = recognize_crops(mgp_model, imgs, boxes, resizer)
+    reads, resizer = recognize_crops(mgp_model, imgs, boxes, resizer, polys=polys if crop == 'polygon' else None)
     for r, m in zip(owner, reads):
         r['mgp_text'], r['mgp_conf'], r['mgp_choice'] = m['char_text'], m['conf'], m['choice']
         r['mgp_ids'] = dict(char=m['char_ids'], bpe=m['bpe_ids'], wp=m['wp_ids'])

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OMP_ABI_VERSION 22
+#define OMP_ABI_VERSION 23
 #define OMP_MAX_DEC_LAYERS 8
 
 enum { OMP_OK = 0, OMP_ERR_LAUNCH = -5, OMP_ERR_INVALID = -22, OMP_ERR_UNSUPPORTED = -95 };
@@ -559,6 +559,40 @@ int omp_resize_normalize_pad(const uint8_t* src, int64_t src_pitch, int in_h, in
                              const int32_t* xcoef, int ksx, const int32_t* ybounds, const int32_t* ycoef, int ksy,
                              const float* lut, float* dst, uint8_t* mask, int out_h, int out_w, int dst_h,
                              int dst_w, omp_stream_t s);
+
+/* ---- word crops for the recogniser, a chunk per launch ------
+ * The reference ships no glue between its spotter and its recogniser; these two stand for what a curved-text reader
+ * puts there (BezierAlign and its relatives) followed by MGP-STR's own crop transform (OCR/MGP-STR/dataset.py:462:
+ * image.resize((imgW, imgH), Image.BICUBIC) + ToTensor), for ALL crops of a chunk at once.  Descriptor tables live in
+ * device memory, one row per crop; utils/word_crops.py packs them. */
+typedef struct omp_rectify_desc {
+  const uint8_t* src;   /* the crop's source image: uint8 HWC RGB on the device */
+  int64_t pitch;        /* bytes per source row */
+  int32_t w, h;         /* source size: sample coordinates clamp to it */
+  int32_t sh, sw;       /* strip size, each in [1, 4096] */
+  int64_t strip_off;    /* byte offset of the packed sh x sw x 3 strip in the scratch buffer */
+  int64_t tile0;        /* tiles (64 columns x 4 rows) of all earlier crops: ascending, 0 for the first */
+  int64_t pq[32];       /* the 16 (x, y) points in original-image pixels, 16 fractional bits: 8 along the top edge in
+                           reading order, then 8 along the bottom edge walking back (utils/misc.py: bezier2polygon) */
+} omp_rectify_desc;
+typedef struct omp_resize_desc {
+  const uint8_t* src;   /* uint8 HWC RGB crop on the device (a strip, or a box of an image) */
+  int64_t pitch;        /* bytes per crop row */
+  int32_t in_h, in_w;
+  int32_t xb, kx, ksx;  /* offsets (in int32 entries) of the x bounds [out_w][2] and coefficients [out_w][ksx] in the packed
+                           table; ksx = 0: the width does not change */
+  int32_t yb, ky, ksy;  /* the same for y */
+} omp_resize_desc;
+/* Samples every crop's source image along its polygon into its strip (integer bilinear, 16 fractional bits; the map is
+ * written out in utils/word_crops.py: rectify_polygon_cpu, which this equals byte for byte).  One launch of total_tiles
+ * workgroups = the sum over crops of ceil(sw / 64) * ceil(sh / 4).  Strips that would not fit scratch_bytes are not
+ * written. */
+int omp_polygon_rectify(const omp_rectify_desc* desc, int n, int64_t total_tiles, uint8_t* scratch,
+                        int64_t scratch_bytes, omp_stream_t s);
+/* The batched form of omp_resize_normalize_pad for crops: Pillow's 8-bit resampler with the tables each descriptor
+ * points to in ONE packed int32 table, then lut (float [3][256]).  dst: fp32 [n, 3, out_h, out_w].  One launch. */
+int omp_resize_crops(const omp_resize_desc* desc, int n, const int32_t* table, int64_t table_len, const float* lut,
+                     float* dst, int out_h, int out_w, omp_stream_t s);
 
 #ifdef __cplusplus
 }
