@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/omp355.h"
 #include "omp355_debug.h"
 
@@ -70,7 +72,7 @@ struct OmpGraphSlot {
 struct OmpProfClass;   // api.hip
 struct omp_ctx {
   // kernel selectors (omp_debug_*): 0 = the measured default everywhere
-  int force_gemm = 0;        // 0 auto, 3 rows, 4 small split-K, 5 dma 128x128, 6 dma 64x64 ring, 9 = 256x256 phase-interleaved, 15 = 5 + timestamps
+  int force_gemm = 0;        // 0 auto (gemm.hip: gemm_auto_select), else a row of gemm.hip: GEMM_SELECTORS
   int cross_q4 = 1;          // 1 = LDS-ring kernel for 33..64 rows per image, 64-key chunks, non-temporal DMA; 2 = one block per step; 4 = chunks, temporal; 0 = register streaming
   int cross_nt = 1;          // non-temporal K / V^T loads: 1 = always (the slabs are read once per launch and would evict the decoder weights from the
                              // MALL: 8-image point phase 39.8 -> 37.2 ms, profiles/r03f_ab_*), 2 = only from 32 groups per launch (round 2), 0 = never
@@ -95,6 +97,35 @@ int omp_device_cus(); // compute units of the current device (cached per device;
 bool omp_prof_active(int cls);
 int omp_prof_begin(int cls, hipStream_t st, double work, double bytes = 0.0);   // -> slot; bytes = algorithmic HBM bytes of the launch
 void omp_prof_end(int cls, int slot, hipStream_t st);
+// the measurement bracket of one launch: begins in the constructor when the class is active (cls < 0: no bracket), ends in the destructor -- on
+// every way out of the scope, before an OMP_CHECK_LAUNCH that follows it
+struct OmpProfScope {
+  OmpProfScope(int cls, hipStream_t st, double work, double bytes = 0.0)
+      : cls_(cls), slot_(cls >= 0 && omp_prof_active(cls) ? omp_prof_begin(cls, st, work, bytes) : -1), st_(st) {}
+  ~OmpProfScope() { if (slot_ >= 0) omp_prof_end(cls_, slot_, st_); }
+  OmpProfScope(const OmpProfScope&) = delete;
+  OmpProfScope& operator=(const OmpProfScope&) = delete;
+ private:
+  int cls_, slot_;
+  hipStream_t st_;
+};
+
+// Raise the dynamic LDS limit of kernel Kern to the CU's 160 KB, once per (kernel, device ordinal): pipeline lanes launch from their own host
+// threads, on their own devices.  A lost race only repeats an idempotent attribute call.  `what` names the entry point.
+template <auto Kern>
+inline int omp_raise_lds(const char* what) {
+  static std::atomic<bool> done[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+    if (done[dev].load(std::memory_order_acquire)) return OMP_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess) {
+      done[dev].store(true, std::memory_order_release);
+      return OMP_OK;
+    }
+  }
+  omp_set_error("%s: cannot raise dynamic LDS limit", what);
+  return OMP_ERR_LAUNCH;
+}
 
 // ---------------------------------------------------------------------------------------------
 // scalar conversions

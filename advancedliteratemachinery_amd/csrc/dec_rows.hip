@@ -630,26 +630,12 @@ unsigned xcd_grid(int64_t n_tiles, int mask, int* mask_out) {
   return (unsigned)((n_tiles + n_sel - 1) / n_sel * 8);
 }
 
-template <typename K>
-int raise_lds(K kern, const char* what) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-    omp_set_error("%s: cannot raise dynamic LDS limit", what);
-    return OMP_ERR_LAUNCH;
-  }
-  return OMP_OK;
-}
-
 template <int RTT, int PRO, int TAIL, int ACT>
 int launch_ffn_t(RowsP p, hipStream_t st) {
   constexpr int RT = RTT * 16;
   const size_t smem = (size_t)RT * A_PITCH + TILE_SLACK + RT * H_PITCH + TILE_SLACK + 2 * NW * RT * 4 + 4 * D * 4;
-  auto kern = dec_rows_ffn_kernel<RTT, PRO, TAIL, ACT>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    const int rc = raise_lds(kern, "omp_dec_rows_ffn");
-    if (rc != OMP_OK) return rc;
-    done = true;
-  }
+  constexpr auto kern = dec_rows_ffn_kernel<RTT, PRO, TAIL, ACT>;
+  if (const int rc = omp_raise_lds<kern>("omp_dec_rows_ffn")) return rc;
   const unsigned grid = xcd_grid(((int64_t)p.R + RT - 1) / RT, p.xcd_mask, &p.xcd_mask);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, st, p);
   OMP_CHECK_LAUNCH("omp_dec_rows_ffn");
@@ -674,13 +660,8 @@ template <int RTT>
 int launch_mid_t(RowsP p, hipStream_t st) {
   constexpr int RT = RTT * 16;
   const size_t smem = (size_t)RT * A_PITCH + TILE_SLACK + 2 * NW * RT * 4;
-  auto kern = dec_rows_mid_kernel<RTT>;
-  static bool done = false;
-  if (!done) {
-    const int rc = raise_lds(kern, "omp_dec_rows_mid");
-    if (rc != OMP_OK) return rc;
-    done = true;
-  }
+  constexpr auto kern = dec_rows_mid_kernel<RTT>;
+  if (const int rc = omp_raise_lds<kern>("omp_dec_rows_mid")) return rc;
   const unsigned grid = xcd_grid(((int64_t)p.R + RT - 1) / RT, p.xcd_mask, &p.xcd_mask);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), smem, st, p);
   return OMP_OK;
@@ -697,26 +678,25 @@ extern "C" int omp_dec_rows_mid(const omp_dec_rows_args* a, omp_stream_t s) {
   OMP_CHECK_ARG(a->wave_stride == (int64_t)mul * 128 * 1024 && ((uintptr_t)a->wstream % 16) == 0,
                 "omp_dec_rows_mid: a wave's stream holds %d fragments of 1 KB (wave_stride %lld: not what model/packing.py::pack_rows_mid returns)", mul * 128, (long long)a->wave_stride);
   if (a->x3) {
-    const int slot3 = omp_prof_active(OMP_PROF_ROWS) ? omp_prof_begin(OMP_PROF_ROWS, (hipStream_t)s, 3 * 4.0 * (double)a->R * D * D, (double)a->R * D * (4 + 4 + 4 + 4) + 2.0 * D * D * 4) : -1;
-    const int rc3 = omp_rows_x3_mid(a, (hipStream_t)s);
-    if (slot3 >= 0) omp_prof_end(OMP_PROF_ROWS, slot3, (hipStream_t)s);
-    return rc3;
+    OmpProfScope prof(OMP_PROF_ROWS, (hipStream_t)s, 3 * 4.0 * (double)a->R * D * D, (double)a->R * D * (4 + 4 + 4 + 4) + 2.0 * D * D * 4);
+    return omp_rows_x3_mid(a, (hipStream_t)s);
   }
   RowsP p{};
   p.R = a->R; p.eps = a->eps; p.d_pos = a->d_pos; p.x = a->x; p.att = reinterpret_cast<const bf16_t*>(a->att);
   p.wstream = reinterpret_cast<const char*>(a->wstream); p.wave_stride = a->wave_stride;
   p.out_b = a->out_b; p.ln_g = a->ln_g; p.ln_b = a->ln_b; p.qbias_tab = a->qbias_tab; p.q = reinterpret_cast<bf16_t*>(a->q);
   p.xcd_mask = a->xcd_mask;
-  const int slot = omp_prof_active(OMP_PROF_ROWS) ? omp_prof_begin(OMP_PROF_ROWS, (hipStream_t)s, 4.0 * (double)a->R * D * D, (double)a->R * D * (2 + 4 + 4 + 2) + 2.0 * D * D * 2) : -1;
   int rc;
-  switch (rows_rtt(p.R, 1)) {
-    case 1: rc = launch_mid_t<1>(p, (hipStream_t)s); break;
-    case 2: rc = launch_mid_t<2>(p, (hipStream_t)s); break;
-    case 3: rc = launch_mid_t<3>(p, (hipStream_t)s); break;
-    case 4: rc = launch_mid_t<4>(p, (hipStream_t)s); break;
-    default: rc = launch_mid_t<5>(p, (hipStream_t)s); break;
+  {
+    OmpProfScope prof(OMP_PROF_ROWS, (hipStream_t)s, 4.0 * (double)a->R * D * D, (double)a->R * D * (2 + 4 + 4 + 2) + 2.0 * D * D * 2);
+    switch (rows_rtt(p.R, 1)) {
+      case 1: rc = launch_mid_t<1>(p, (hipStream_t)s); break;
+      case 2: rc = launch_mid_t<2>(p, (hipStream_t)s); break;
+      case 3: rc = launch_mid_t<3>(p, (hipStream_t)s); break;
+      case 4: rc = launch_mid_t<4>(p, (hipStream_t)s); break;
+      default: rc = launch_mid_t<5>(p, (hipStream_t)s); break;
+    }
   }
-  if (slot >= 0) omp_prof_end(OMP_PROF_ROWS, slot, (hipStream_t)s);
   if (rc != OMP_OK) return rc;
   OMP_CHECK_LAUNCH("omp_dec_rows_mid");
   return OMP_OK;
@@ -738,10 +718,8 @@ extern "C" int omp_dec_rows_ffn(const omp_dec_rows_args* a, omp_stream_t s) {
                 "omp_dec_rows_ffn: a wave's stream holds %lld fragments of 1 KB here (wave_stride %lld: not what the packer of this chain returns)", (long long)(mul * frags), (long long)a->wave_stride);
   if (a->x3) {
     const double fl3 = 3 * 2.0 * (double)a->R * D * ((a->prologue == 0 ? D + 8.0 * D : 0.0) + (a->tail == 0 ? 3.0 * D : 2.0 * D + a->vocab));
-    const int slot3 = omp_prof_active(OMP_PROF_ROWS) ? omp_prof_begin(OMP_PROF_ROWS, (hipStream_t)s, fl3, (double)a->R * D * (4 + 4 + 4) + (double)a->R * (a->tail == 0 ? 3 * D * 4 : a->vocab * 4) + (double)frags * 2 * 8192) : -1;
-    const int rc3 = omp_rows_x3_ffn(a, (hipStream_t)s);
-    if (slot3 >= 0) omp_prof_end(OMP_PROF_ROWS, slot3, (hipStream_t)s);
-    return rc3;
+    OmpProfScope prof(OMP_PROF_ROWS, (hipStream_t)s, fl3, (double)a->R * D * (4 + 4 + 4) + (double)a->R * (a->tail == 0 ? 3 * D * 4 : a->vocab * 4) + (double)frags * 2 * 8192);
+    return omp_rows_x3_ffn(a, (hipStream_t)s);
   }
   RowsP p{};
   p.R = a->R; p.eps = a->eps; p.d_pos = a->d_pos; p.x = a->x; p.att = reinterpret_cast<const bf16_t*>(a->att);
@@ -753,12 +731,9 @@ extern "C" int omp_dec_rows_ffn(const omp_dec_rows_args* a, omp_stream_t s) {
   p.xcd_mask = a->xcd_mask;
   hipStream_t st = (hipStream_t)s;
   const double fl = 2.0 * (double)a->R * D * ((a->prologue == 0 ? D + 8.0 * D : 0.0) + (a->tail == 0 ? 3.0 * D : 2.0 * D + a->vocab));
-  const int slot = omp_prof_active(OMP_PROF_ROWS) ? omp_prof_begin(OMP_PROF_ROWS, st, fl, (double)a->R * D * (2 + 4 + 4) + (double)a->R * (a->tail == 0 ? 3 * D * 2 : a->vocab * 4) + (double)frags * 8192) : -1;
-  int rc;
-  if (a->prologue == 0) rc = a->tail == 0 ? launch_ffn<0, 0>(p, st) : launch_ffn<0, 1>(p, st);
-  else rc = a->tail == 0 ? launch_ffn<1, 0>(p, st) : launch_ffn<1, 1>(p, st);
-  if (slot >= 0) omp_prof_end(OMP_PROF_ROWS, slot, st);
-  return rc;
+  OmpProfScope prof(OMP_PROF_ROWS, st, fl, (double)a->R * D * (2 + 4 + 4) + (double)a->R * (a->tail == 0 ? 3 * D * 2 : a->vocab * 4) + (double)frags * 8192);
+  if (a->prologue == 0) return a->tail == 0 ? launch_ffn<0, 0>(p, st) : launch_ffn<0, 1>(p, st);
+  return a->tail == 0 ? launch_ffn<1, 0>(p, st) : launch_ffn<1, 1>(p, st);
 }
 
 extern "C" int omp_dec_rows_tile(void) { return omp_rows_tile(); }
@@ -797,10 +772,8 @@ extern "C" int omp_swin_rows_block(const omp_swin_rows_args* a, omp_stream_t s) 
   if (a->x3) {
     const double fl3 = 3 * 2.0 * (double)a->M * D * ((a->mode == 1 ? D + 8.0 * D : 0.0) + (tail_qkv ? 3.0 * D : 0.0));
     const double by3 = (double)a->M * D * (a->mode == 1 ? 4 + 4 + 4 : 4) + (tail_qkv ? (double)a->M * 3 * D * 4 : 0.0) + (double)frags * 2 * 8192;
-    const int slot3 = omp_prof_active(OMP_PROF_MLP) ? omp_prof_begin(OMP_PROF_MLP, (hipStream_t)s, fl3, by3) : -1;
-    const int rc3 = omp_rows_x3_swin(a, (hipStream_t)s);
-    if (slot3 >= 0) omp_prof_end(OMP_PROF_MLP, slot3, (hipStream_t)s);
-    return rc3;
+    OmpProfScope prof(OMP_PROF_MLP, (hipStream_t)s, fl3, by3);
+    return omp_rows_x3_swin(a, (hipStream_t)s);
   }
   RowsP p{};
   p.R = (int)a->M; p.eps = a->eps; p.d_pos = nullptr; p.x = a->x; p.att = reinterpret_cast<const bf16_t*>(a->att);
@@ -811,10 +784,7 @@ extern "C" int omp_swin_rows_block(const omp_swin_rows_args* a, omp_stream_t s) 
   hipStream_t st = (hipStream_t)s;
   const double fl = 2.0 * (double)a->M * D * ((a->mode == 1 ? D + 8.0 * D : 0.0) + (tail_qkv ? 3.0 * D : 0.0));
   const double by = (double)a->M * D * (a->mode == 1 ? 2 + 4 + 4 : 4) + (tail_qkv ? (double)a->M * 3 * D * 2 : 0.0) + (double)frags * 8192;
-  const int slot = omp_prof_active(OMP_PROF_MLP) ? omp_prof_begin(OMP_PROF_MLP, st, fl, by) : -1;
-  int rc;
-  if (a->mode == 0) rc = launch_ffn<2, 0, 1>(p, st);
-  else rc = tail_qkv ? launch_ffn<0, 0, 1>(p, st) : launch_ffn<0, 2, 1>(p, st);
-  if (slot >= 0) omp_prof_end(OMP_PROF_MLP, slot, st);
-  return rc;
+  OmpProfScope prof(OMP_PROF_MLP, st, fl, by);
+  if (a->mode == 0) return launch_ffn<2, 0, 1>(p, st);
+  return tail_qkv ? launch_ffn<0, 0, 1>(p, st) : launch_ffn<0, 2, 1>(p, st);
 }

@@ -476,25 +476,11 @@ __global__ __launch_bounds__(NW * 64) void dec_rows_x3_ffn_kernel(Rows3P p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <typename K>
-int raise_lds(K kern, const char* what) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-    omp_set_error("%s: cannot raise dynamic LDS limit", what);
-    return OMP_ERR_LAUNCH;
-  }
-  return OMP_OK;
-}
-
 template <int PRO, int TAIL, int ACT>
 int launch_ffn3(const Rows3P& p, hipStream_t st) {
   const size_t smem = (size_t)2 * TILE_BYTES + 2 * HT_BYTES + 2 * NW * RT3 * 4 + 4 * D * 4;
-  auto kern = dec_rows_x3_ffn_kernel<PRO, TAIL, ACT>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    const int rc = raise_lds(kern, "row-owner chain (bf16x3)");
-    if (rc != OMP_OK) return rc;
-    done = true;
-  }
+  constexpr auto kern = dec_rows_x3_ffn_kernel<PRO, TAIL, ACT>;
+  if (const int rc = omp_raise_lds<kern>("row-owner chain (bf16x3)")) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(((int64_t)p.R + RT3 - 1) / RT3)), dim3(NW * 64), smem, st, p);
   OMP_CHECK_LAUNCH("row-owner chain (bf16x3)");
   return OMP_OK;
@@ -511,12 +497,7 @@ int omp_rows_x3_mid(const omp_dec_rows_args* a, hipStream_t st) {
   p.wstream = reinterpret_cast<const char*>(a->wstream); p.wave_stride = a->wave_stride;
   p.out_b = a->out_b; p.ln_g = a->ln_g; p.ln_b = a->ln_b; p.qbias_tab = a->qbias_tab; p.q = reinterpret_cast<float*>(a->q);
   const size_t smem = (size_t)2 * TILE_BYTES + 2 * NW * RT3 * 4;
-  static bool done = false;
-  if (!done) {
-    const int rc = raise_lds(dec_rows_x3_mid_kernel, "omp_dec_rows_mid(bf16x3)");
-    if (rc != OMP_OK) return rc;
-    done = true;
-  }
+  if (const int rc = omp_raise_lds<dec_rows_x3_mid_kernel>("omp_dec_rows_mid(bf16x3)")) return rc;
   hipLaunchKernelGGL(dec_rows_x3_mid_kernel, dim3((unsigned)(((int64_t)p.R + RT3 - 1) / RT3)), dim3(NW * 64), smem, st, p);
   OMP_CHECK_LAUNCH("omp_dec_rows_mid(bf16x3)");
   return OMP_OK;

@@ -1400,16 +1400,9 @@ template <typename T, int QT, int PD, bool NT = false>
 int launch_cross_t(const CrossP& cp, int n_groups, int S, hipStream_t st) {
   constexpr int NW = 4;
   const size_t smem = (size_t)NW * QT * 16 * CROSS_PSTR * sizeof(float);
-  auto kern = dec_cross_attn_kernel<T, NW, QT, PD, NT>;
+  constexpr auto kern = dec_cross_attn_kernel<T, NW, QT, PD, NT>;
   if (smem > 48 * 1024) {
-    static bool done = false;   // per template instantiation
-    if (!done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        omp_set_error("omp_dec_cross_attn_step: cannot raise dynamic LDS limit");
-        return OMP_ERR_LAUNCH;
-      }
-      done = true;
-    }
+    if (const int rc = omp_raise_lds<kern>("omp_dec_cross_attn_step")) return rc;
   }
   hipLaunchKernelGGL(kern, dim3(n_groups, cp.nH, S), dim3(NW * 64), smem, st, cp);
   return OMP_OK;
@@ -1434,15 +1427,8 @@ int launch_merge(const CrossP& cp, int S, hipStream_t st) {
 template <typename T, int NS, int CH, bool NT>
 int launch_cross_q4(const CrossP& cp, int n_groups, int S, hipStream_t st) {
   const size_t smem = (size_t)NS * 8192 * CrossTraits<T>::PL;
-  auto kern = dec_cross_attn_q4_kernel<T, NS, CH, NT>;
-  static bool done = false;   // per template instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_dec_cross_attn_step: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = dec_cross_attn_q4_kernel<T, NS, CH, NT>;
+  if (const int rc = omp_raise_lds<kern>("omp_dec_cross_attn_step")) return rc;
   hipLaunchKernelGGL(kern, dim3(n_groups, cp.nH, S), dim3(256), smem, st, cp);
   return OMP_OK;
 }

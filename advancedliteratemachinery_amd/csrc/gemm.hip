@@ -17,7 +17,6 @@
 // are 8/16-byte vectors instead of 4 scalar stores.
 #include <type_traits>
 
-#include <atomic>
 #include "common.h"
 
 namespace {
@@ -549,15 +548,8 @@ int launch_dma(GemmP& p, hipStream_t st) {
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int EBYTES = BM * (BN + 4) * 4;
   constexpr size_t smem = (NS * STAGE > EBYTES) ? NS * STAGE : EBYTES;
-  auto kern = gemm_dma<T, TOut, BM, BN, NS, TRACE>;
-  static bool done = false;   // per template instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = gemm_dma<T, TOut, BM, BN, NS, TRACE>;
+  if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   p.tiles_m = (int)ceil_div64(p.M, BM); p.tiles_n = (int)ceil_div64(p.N, BN);
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(256), smem, st, p);
   return OMP_OK;
@@ -760,16 +752,9 @@ int launch_small_t(const GemmP& p, hipStream_t st) {
   const size_t red = 4 * MF * 64 * sizeof(f32x4);
   const size_t ab = LN ? (size_t)MF * 16 * (p.K * sizeof(T) + 16) : 0;
   const size_t smem = red + ab;
-  auto kern = gemm_small<T, TOut, MF, LN>;
+  constexpr auto kern = gemm_small<T, TOut, MF, LN>;
   if (smem > 48 * 1024) {
-    static bool done = false;   // per template instantiation
-    if (!done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-        return OMP_ERR_LAUNCH;
-      }
-      done = true;
-    }
+    if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div64(p.N, 16)), dim3(256), smem, st, p);
   OMP_CHECK_LAUNCH("omp_gemm_bias_act(small)");
@@ -791,228 +776,188 @@ inline double gemm_alg_bytes(const GemmP& p, size_t esz, size_t osz) {
          (double)p.M * p.N * (double)osz * (1.0 + (p.residual != nullptr ? 1.0 : 0.0) + (p.C2 != nullptr ? 1.0 : 0.0));
 }
 
+// The split-K small-M kernel (selector 4; also every product with a LayerNorm prologue)
+inline bool gemm_small_ok(const GemmP& p, bool bf16_in, bool) {
+  const int kq = 4 * (bf16_in ? Mma<bf16_t>::KSTEP : Mma<float>::KSTEP);
+  return p.a_wrap == 0 && !p.split_out && p.M <= 64 && p.K % kq == 0 && !p.trans_out && (p.ln_g == nullptr || p.K <= 1024);
+}
+// the ablations of gemm_4w (12..14) and gemm_4w_r (17): plain bf16 products of their parent kernel
+inline bool gemm4w_plain_ok(const GemmP& p, bool bf16_in, bool bf16_out) { return gemm4w_ok(p, bf16_in, bf16_out) && p.store_mode == OMP_STORE_PLAIN && !p.split_out; }
+inline bool gemm4wr_plain_ok(const GemmP& p, bool bf16_in, bool bf16_out) { return gemm4wr_ok(p, bf16_in, bf16_out) && !p.split_out; }
+
+// THE table of kernel selectors (omp_debug_force_gemm_kernel; 0 = gemm_auto_select): one row per selector with everything launch_gemm knows
+// about it except the launch call itself (gemm_launch_sel).  A new kernel adds a row here and a case there.
+enum { GEMM_OUT_ANY = 0, GEMM_OUT_BF16 = 1, GEMM_OUT_F32 = 2 };
+struct GemmSel {
+  int sel;
+  const char* name;
+  bool bf16_in;     // bf16 operands only
+  int out;          // GEMM_OUT_*: destination types it is built for
+  bool c2;          // takes a second destination (C2)
+  bool prof;        // bracketed for bench.py's matrix-core roofline legs (class by M >= 32768)
+  int trace_tile;   // > 0: development kernel with per-workgroup timestamps, needs omp_debug_set_gemm_trace with a slot per tile of this size
+  bool (*ok)(const GemmP&, bool bf16_in, bool bf16_out);   // the products it takes; nullptr = all
+  const char* takes;                                        // ... in words, for the refusal
+};
+constexpr GemmSel GEMM_SELECTORS[] = {
+    {3, "row streaming", false, GEMM_OUT_ANY, false, false, 0, nullptr, ""},
+    {4, "split-K small-M", false, GEMM_OUT_ANY, false, false, 0, gemm_small_ok,
+     "M <= 64, K a multiple of four k-steps (bf16: 128, fp32: 64), no trans_out, no split-bf16 operands / destinations, K <= 1024 behind the fused LayerNorm"},
+    {5, "128x128 tiles", false, GEMM_OUT_ANY, true, true, 0, nullptr, ""},
+    {6, "64x64 tiles", false, GEMM_OUT_ANY, true, false, 0, nullptr, ""},
+    {9, "256x256 tiles (gemm256.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm256_ok,
+     "K % 64 == 0, K >= 128, N % 8 == 0 (blocked K / V^T slabs: bf16 only)"},
+    {10, "256x256 tiles on four waves (gemm4w.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4w_ok, "the shapes of selector 9"},
+    {11, "256x256 tiles on four waves; alias of 10", true, GEMM_OUT_ANY, true, true, 0, gemm4w_ok, "the shapes of selector 9"},
+    // development: gemm_4w ablations (wrong results, valid timing), plain bf16 destination only
+    {12, "gemm_4w ablation 1", true, GEMM_OUT_BF16, false, false, 0, gemm4w_plain_ok, "plain bf16 products"},
+    {13, "gemm_4w ablation 2", true, GEMM_OUT_BF16, false, false, 0, gemm4w_plain_ok, "plain bf16 products"},
+    {14, "gemm_4w ablation 3", true, GEMM_OUT_BF16, false, false, 0, gemm4w_plain_ok, "plain bf16 products"},
+    // development: gemm_dma<128,128,2> with per-workgroup phase timestamps
+    {15, "128x128 tiles with timestamps", false, GEMM_OUT_ANY, true, false, 128, nullptr, ""},
+    // 256x256 tiles on four waves, weights streamed into registers (gemm4wr.inc); 17: without its MFMAs (wrong results, valid timing);
+    // 18: per-workgroup phase timestamps (tools/gemm4wr_trace.py)
+    {16, "register-streamed weights (gemm4wr.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4wr_ok,
+     "row-major destinations of selector 9 with K % 256 == 0"},
+    {17, "register-streamed weights without MFMAs", true, GEMM_OUT_BF16, false, true, 0, gemm4wr_plain_ok, "plain bf16 products of selector 16"},
+    {18, "register-streamed weights with timestamps", true, GEMM_OUT_ANY, true, true, 256, gemm4wr_ok,
+     "row-major destinations of selector 9 with K % 256 == 0"},
+    // persistent 256x256 tiles on four waves, register-only epilogue (gemm4wp.inc); 21: 2/3 of its operand bytes (wrong results, valid timing)
+    {20, "persistent four-wave tiles (gemm4wp.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4wp_ok,
+     "row-major destinations with M, N, K multiples of 256 and 16-byte aligned bias / rows"},
+    {21, "persistent four-wave tiles, 2/3 of the operand bytes", true, GEMM_OUT_F32, true, true, 0, gemm4wp_ok, "the fp32 products of selector 20"},
+    // bf16x3: the three products fused over shared operand tiles (gemm4wp.inc, X3)
+    {22, "fused bf16x3 products", true, GEMM_OUT_ANY, true, true, 0, gemm4wx3_ok,
+     "bf16x3 operands (a_wrap = 2 K0, K = 3 K0, K0 % 128 == 0), M and N multiples of 256, fp32 or split destination"},
+};
+inline const GemmSel* gemm_selector(int which) {
+  for (const GemmSel& s : GEMM_SELECTORS)
+    if (s.sel == which) return &s;
+  return nullptr;
+}
+
+// The ONE place that decides whether a selector takes a product: the launch path and omp_debug_gemm_choice both ask here, so the
+// host-logic test of the dispatch table cannot report a selector for arguments the real call refuses.  Sets the error string on a refusal.
+inline bool gemm_accepts(const GemmSel& s, const GemmP& p, bool bf16_in, bool bf16_out) {
+  const char* why = nullptr;
+  if (p.C2 != nullptr && !s.c2) why = "no second destination (C2)";
+  else if (s.bf16_in && !bf16_in) why = "bf16 operands only";
+  else if (s.out == GEMM_OUT_BF16 && !bf16_out) why = "bf16 destinations only";
+  else if (s.out == GEMM_OUT_F32 && bf16_out) why = "fp32 destinations only";
+  else if (s.ok != nullptr && !s.ok(p, bf16_in, bf16_out)) why = s.takes;
+  if (why == nullptr) return true;
+  omp_set_error("omp_gemm_bias_act: kernel selector %d (%s) does not take this product: %s", s.sel, s.name, why);
+  return false;
+}
+
+// the measured default (force_gemm == 0) for a product neither the small-M kernel nor the row statistics claim
+inline int gemm_auto_select(const GemmP& p, bool bf16_in, bool bf16_out) {
+  int which;
+  // round 4 (profiles/r04b_kbench_dec_rows*.txt, the 10240-row polygon / recognition phases of a 160-image engine call): 64x64
+  // tiles only below 256 tiles of 128x128 (they lose 10-25 % to the 128x128 kernel at 320 tiles, at K = 512 and at the bf16x3
+  // engine's K = 1536 / 6144 alike)
+  if (p.M <= 64) which = 3;
+  else if (ceil_div64(p.M, 128) * ceil_div64(p.N, 128) < 256) which = 6;
+  else which = 5;
+  // 256x256 phase-interleaved tiles once they fill the chip and the output is wide enough for a 256-column tile to pay
+  // (profiles/r02g_kbench_gemm_256.txt: wins on every Swin qkv / fc1 / fc2 / proj shape of stages 1-3 with >= 256 tiles, loses
+  // at N = 128 and on half-empty grids).  "Fill the chip" = the last round of tiles over the 256 CUs is not mostly idle: 240
+  // tiles (one round, 94 %) win, 320 tiles (two rounds, 62 %) lose to the 128x128 kernel (r04b)
+  if (bf16_in) {
+    const int64_t t256 = ceil_div64(p.M, 256) * ceil_div64(p.N, 256);
+    const bool fills = t256 >= 192 && 4 * t256 >= 3 * 256 * ceil_div64(t256, 256);
+    if (which == 5 && p.N >= 256 && fills && gemm256_ok(p, true, bf16_out)) which = 9;
+    // the four-wave kernel (gemm4w.inc) produces the same bits; measured against gemm_256 per shape (profiles/r04f_kbench_gemm_4w_v2_*):
+    // equal within the box-to-box spread on most, 7-13 % faster on the half-million-row products of stage 1 without an activation,
+    // 7-13 % slower behind a GELU epilogue (four waves instead of eight do the vector work) -- it takes the former
+    if (which == 9 && p.act == OMP_ACT_NONE && p.store_mode == OMP_STORE_PLAIN && p.M >= 262144 && (p.K >= 1024 || p.N >= 768)) which = 10;
+    // the persistent four-wave kernel (gemm4wp.inc; same bits again) where its register-only epilogue and its missing prologues pay
+    // (profiles/r04s_kbench_gemm_4w_p_*.txt, r04v_kbench_ab_k9_k20.txt: three boxes): behind a GELU on a bf16 destination (+9 % at
+    // K = 512, +3-13 % at K = 768, +23-30 % at K = 256, equal at K = 1024) and on the K = 768 products without a residual (ViT-B qkv
+    // +7 %, the bf16x3 stage-1 qkv +7 % over gemm_4w); equal or behind gemm_256 elsewhere (K = 256 without GELU: +12 % on one box,
+    // -7 % on another; long K: the operand stream paces both kernels)
+    if ((which == 9 || which == 10) && !p.split_out && gemm4wp_ok(p, true, bf16_out) &&
+        ((p.act == OMP_ACT_GELU && bf16_out) || (p.K == 768 && p.residual == nullptr && p.N >= 768 && p.act == OMP_ACT_NONE)))
+      which = 20;
+    // bf16x3 operands: the three products fused over shared operand tiles (gemm4wp.inc, X3) wherever a 256x256-tile kernel was chosen
+    // and the shape has no ragged edge -- 2/3 of the operand bytes; faster on every encoder product of the parity engine
+    // (profiles/r04y_kbench_gemm_x3_fused.txt: -1...-17 %).  Its summation order is chunk by chunk, not plane by plane: equal to the
+    // three-pass kernels within fp32 rounding, not bit for bit.
+    if ((which == 9 || which == 10 || which == 20) && gemm4wx3_ok(p, true, bf16_out)) which = 22;
+  }
+  return which;
+}
+
+// the launch of selector `which` (4 excepted: launch_gemm calls launch_small itself): a switch of direct calls (the few-row decoder step is bound by its launch rate and comes through here)
+template <typename T, typename TOut>
+int gemm_launch_sel(int which, GemmP& p, hipStream_t st) {
+  constexpr bool BI = std::is_same<T, bf16_t>::value, BO = std::is_same<TOut, bf16_t>::value;
+  // (cases in the order the kernels have always been instantiated in: it is their order in the code object, which kept the device code of this
+  // file identical across the move to the table.  Nothing else depends on it: sort the cases whenever that proof is no longer wanted.)
+  switch (which) {
+    case 5: return launch_dma<T, TOut, 128, 128, 2>(p, st);
+    case 6:
+      // mid-size problems (decoder phases with 65..~4000 rows, small-image encoders): 64x64 tiles and a deep
+      // ring so that the K extent is in flight at once; a shallower ring (2 workgroups per CU) once the grid
+      // is large enough to want the occupancy instead
+      return (ceil_div64(p.M, 64) * ceil_div64(p.N, 64) <= 512) ? launch_dma<T, TOut, 64, 64, 8>(p, st) : launch_dma<T, TOut, 64, 64, 4>(p, st);
+    case 9: if constexpr (BI) return launch_256<TOut>(p, st); break;
+    case 10: case 11: if constexpr (BI) return launch_4w<TOut, 5>(p, st); break;
+    case 12: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 1>(p, st); break;
+    case 13: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 2>(p, st); break;
+    case 14: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 3>(p, st); break;
+    case 16: if constexpr (BI) return launch_4wr<TOut>(p, st); break;
+    case 18: if constexpr (BI) return launch_4wr_t<TOut, false, 4>(p, st); break;
+    case 17: if constexpr (BI && BO) return launch_4wr_t<TOut, false, 3>(p, st); break;
+    case 20: if constexpr (BI) return launch_4wp<TOut>(p, st); break;
+    case 21: if constexpr (BI && !BO) return launch_4wp_t<TOut, false, 5>(p, st); break;
+    case 22: if constexpr (BI) return launch_4wx3<TOut>(p, st); break;
+    case 15: return launch_dma<T, TOut, 128, 128, 2, true>(p, st);
+    case 3: {
+      dim3 grid((unsigned)ceil_div64(p.N, 64), (unsigned)ceil_div64(p.M, 16));
+      hipLaunchKernelGGL((gemm_rows<T, TOut>), grid, dim3(256), 0, st, p);
+      return OMP_OK;
+    }
+    default: break;
+  }
+  omp_set_error("omp_gemm_bias_act: kernel selector %d is not built for these types", which);   // gemm_accepts refuses them first
+  return OMP_ERR_INVALID;
+}
+
 template <typename T, typename TOut>
 int launch_gemm(const GemmP& p0, hipStream_t st) {
   GemmP p = p0;
   omp_ctx& cx = omp_cur();
+  constexpr bool BI = std::is_same<T, bf16_t>::value, BO = std::is_same<TOut, bf16_t>::value;
   int which = cx.force_gemm;
-  const int kq = 4 * Mma<T>::KSTEP;
-  if (p.ln_g != nullptr || which == 4 || (which == 0 && p.small_hint && p.M <= 64 && p.K % kq == 0)) {
-    if (p.a_wrap > 0 || p.split_out) {
-      omp_set_error("omp_gemm_bias_act: the split-K small-M kernel takes no split-bf16 operands / destinations");
-      return OMP_ERR_UNSUPPORTED;
-    }
-    if (p.M > 64 || p.K % kq != 0 || p.trans_out) {
-      omp_set_error("omp_gemm_bias_act: split-K small-M kernel needs M <= 64, K %% %d == 0, no trans_out", kq);
-      return OMP_ERR_UNSUPPORTED;
-    }
-    if (p.ln_g != nullptr && p.K > 1024) {
-      omp_set_error("omp_gemm_bias_act: fused LayerNorm supports K <= 1024");
-      return OMP_ERR_UNSUPPORTED;
-    }
-    if (cx.gemm_choice_only) { cx.gemm_last_choice = 4; return OMP_OK; }
-    return launch_small<T, TOut>(p, st);
+  if (p.store_mode == OMP_STORE_ROWSTAT) which = 5;   // the row statistics live in the 128 x 128 kernel's epilogue, whatever is forced
+  else if (p.ln_g != nullptr || (which == 0 && p.small_hint && p.M <= 64 && p.K % (4 * Mma<T>::KSTEP) == 0)) which = 4;
+  else if (which == 0) which = gemm_auto_select(p, BI, BO);
+  const GemmSel* sel = gemm_selector(which);
+  if (sel == nullptr) {
+    omp_set_error("omp_gemm_bias_act: unknown kernel selector %d", which);
+    // omp_debug_gemm_choice and a call with a second destination have always answered UNSUPPORTED here, a plain launch INVALID
+    return cx.gemm_choice_only || p.C2 != nullptr ? OMP_ERR_UNSUPPORTED : OMP_ERR_INVALID;
   }
-  if (p.store_mode == OMP_STORE_ROWSTAT) which = 5;   // the row statistics live in the 128 x 128 kernel's epilogue
-  if (which == 0) {
-    // round 4 (profiles/r04b_kbench_dec_rows*.txt, the 10240-row polygon / recognition phases of a 160-image engine call): 64x64
-    // tiles only below 256 tiles of 128x128 (they lose 10-25 % to the 128x128 kernel at 320 tiles, at K = 512 and at the bf16x3
-    // engine's K = 1536 / 6144 alike)
-    if (p.M <= 64) which = 3;
-    else if (ceil_div64(p.M, 128) * ceil_div64(p.N, 128) < 256) which = 6;
-    else which = 5;
-    // 256x256 phase-interleaved tiles once they fill the chip and the output is wide enough for a 256-column tile to pay
-    // (profiles/r02g_kbench_gemm_256.txt: wins on every Swin qkv / fc1 / fc2 / proj shape of stages 1-3 with >= 256 tiles, loses
-    // at N = 128 and on half-empty grids).  "Fill the chip" = the last round of tiles over the 256 CUs is not mostly idle: 240
-    // tiles (one round, 94 %) win, 320 tiles (two rounds, 62 %) lose to the 128x128 kernel (r04b)
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      const int64_t t256 = ceil_div64(p.M, 256) * ceil_div64(p.N, 256);
-      const bool fills = t256 >= 192 && 4 * t256 >= 3 * 256 * ceil_div64(t256, 256);
-      if (which == 5 && p.N >= 256 && fills && gemm256_ok(p, true, std::is_same<TOut, bf16_t>::value)) which = 9;
-      // the four-wave kernel (gemm4w.inc) produces the same bits; measured against gemm_256 per shape (profiles/r04f_kbench_gemm_4w_v2_*):
-      // equal within the box-to-box spread on most, 7-13 % faster on the half-million-row products of stage 1 without an activation,
-      // 7-13 % slower behind a GELU epilogue (four waves instead of eight do the vector work) -- it takes the former
-      if (which == 9 && p.act == OMP_ACT_NONE && p.store_mode == OMP_STORE_PLAIN && p.M >= 262144 && (p.K >= 1024 || p.N >= 768)) which = 10;
-      // the persistent four-wave kernel (gemm4wp.inc; same bits again) where its register-only epilogue and its missing prologues pay
-      // (profiles/r04s_kbench_gemm_4w_p_*.txt, r04v_kbench_ab_k9_k20.txt: three boxes): behind a GELU on a bf16 destination (+9 % at
-      // K = 512, +3-13 % at K = 768, +23-30 % at K = 256, equal at K = 1024) and on the K = 768 products without a residual (ViT-B qkv
-      // +7 %, the bf16x3 stage-1 qkv +7 % over gemm_4w); equal or behind gemm_256 elsewhere (K = 256 without GELU: +12 % on one box,
-      // -7 % on another; long K: the operand stream paces both kernels)
-      if ((which == 9 || which == 10) && !p.split_out && gemm4wp_ok(p, true, std::is_same<TOut, bf16_t>::value) &&
-          ((p.act == OMP_ACT_GELU && std::is_same<TOut, bf16_t>::value) || (p.K == 768 && p.residual == nullptr && p.N >= 768 && p.act == OMP_ACT_NONE)))
-        which = 20;
-      // bf16x3 operands: the three products fused over shared operand tiles (gemm4wp.inc, X3) wherever a 256x256-tile kernel was chosen
-      // and the shape has no ragged edge -- 2/3 of the operand bytes; faster on every encoder product of the parity engine
-      // (profiles/r04y_kbench_gemm_x3_fused.txt: -1...-17 %).  Its summation order is chunk by chunk, not plane by plane: equal to the
-      // three-pass kernels within fp32 rounding, not bit for bit.
-      if ((which == 9 || which == 10 || which == 20) && gemm4wx3_ok(p, true, std::is_same<TOut, bf16_t>::value)) which = 22;
-    }
-  }
-  if (cx.gemm_choice_only) {
-    // omp_debug_gemm_choice: the dispatch table is host logic, testable without a GPU.  It reports a selector only for arguments the
-    // launch path below accepts -- a forced selector that does not take the product (no second destination, a shape its tiles do not
-    // cover, non-bf16 operands) is the launch path's OMP_ERR_UNSUPPORTED here too
-    bool ok = true;
-    constexpr bool BO = std::is_same<TOut, bf16_t>::value;
-    if (p.C2 != nullptr && which != 5 && which != 6 && which != 9 && which != 10 && which != 11 && which != 15 && which != 16 && which != 18 && which != 20 && which != 21 && which != 22) ok = false;
-    else if (which == 9 || (which >= 10 && which <= 14) || (which >= 16 && which <= 18) || (which >= 20 && which <= 22)) {
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (which == 9) ok = gemm256_ok(p, true, BO);
-        else if (which == 10 || which == 11) ok = gemm4w_ok(p, true, BO);
-        else if (which >= 12 && which <= 14) ok = BO && gemm4w_ok(p, true, true) && p.store_mode == OMP_STORE_PLAIN && !p.split_out;
-        else if (which >= 16 && which <= 18) ok = gemm4wr_ok(p, true, BO) && (which != 17 || (BO && !p.split_out));
-        else if (which == 20 || which == 21) ok = gemm4wp_ok(p, true, BO) && (which != 21 || !BO);
-        else ok = gemm4wx3_ok(p, true, BO);
-      } else {
-        ok = false;
-      }
-    } else if (which != 3 && which != 5 && which != 6 && which != 15) {
-      ok = false;
-    }
-    if (!ok) {
-      omp_set_error("omp_gemm_bias_act: kernel selector %d does not take this product", which);
-      return OMP_ERR_UNSUPPORTED;
-    }
-    cx.gemm_last_choice = which;
-    return OMP_OK;
-  }
-  if (p.C2 != nullptr && which != 5 && which != 6 && which != 9 && which != 10 && which != 11 && which != 15 && which != 16 && which != 18 && which != 20 && which != 21 && which != 22) {
-    omp_set_error("omp_gemm_bias_act: kernel selector %d has no second destination (C2)", which);
-    return OMP_ERR_UNSUPPORTED;
-  }
-  if (which == 5) {
-    // bench.py's matrix-core roofline leg: hipEvent bracket + flop count of the large-M GEMMs
-    const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-    const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-    int rc = launch_dma<T, TOut, 128, 128, 2>(p, st);
-    if (slot >= 0) omp_prof_end(pcls, slot, st);
-    if (rc != OMP_OK) return rc;
-  } else if (which == 6) {
-    // mid-size problems (decoder phases with 65..~4000 rows, small-image encoders): 64x64 tiles and a deep
-    // ring so that the K extent is in flight at once; a shallower ring (2 workgroups per CU) once the grid
-    // is large enough to want the occupancy instead
-    int rc = (ceil_div64(p.M, 64) * ceil_div64(p.N, 64) <= 512) ? launch_dma<T, TOut, 64, 64, 8>(p, st)
-                                                                 : launch_dma<T, TOut, 64, 64, 4>(p, st);
-    if (rc != OMP_OK) return rc;
-  } else if (which == 9) {           // 256x256 phase-interleaved kernel (gemm256.inc)
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!gemm256_ok(p, true, std::is_same<TOut, bf16_t>::value)) {
-        omp_set_error("omp_gemm_bias_act: selector 9 (256x256 tiles) needs bf16 operands, K %% 64 == 0, K >= 128, N %% 8 == 0 (blocked K / V^T slabs: bf16 only)");
-        return OMP_ERR_UNSUPPORTED;
-      }
-      const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-    const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-      int rc = launch_256<TOut>(p, st);
-      if (slot >= 0) omp_prof_end(pcls, slot, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selector 9 (256x256 tiles) is bf16-only");
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which == 10 || which == 11) {   // 256x256 tiles on four waves (gemm4w.inc); 11 is kept as an alias of 10
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!gemm4w_ok(p, true, std::is_same<TOut, bf16_t>::value)) {
-        omp_set_error("omp_gemm_bias_act: selector %d (256x256 tiles on four waves) takes the shapes of selector 9", which);
-        return OMP_ERR_UNSUPPORTED;
-      }
-      const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-    const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-      int rc = launch_4w<TOut, 5>(p, st);
-      if (slot >= 0) omp_prof_end(pcls, slot, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selector %d (256x256 tiles on four waves) is bf16-only", which);
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which >= 12 && which <= 14) {   // development: gemm_4w ablations (wrong results, valid timing), plain bf16 destination only
-    if constexpr (std::is_same<T, bf16_t>::value && std::is_same<TOut, bf16_t>::value) {
-      if (!gemm4w_ok(p, true, true) || p.store_mode != OMP_STORE_PLAIN || p.split_out) { omp_set_error("omp_gemm_bias_act: selectors 12..14 take plain bf16 products"); return OMP_ERR_UNSUPPORTED; }
-      int rc = which == 12 ? launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 1>(p, st) : which == 13 ? launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 2>(p, st)
-                                                                                                     : launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 3>(p, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selectors 12..14 take plain bf16 products");
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which >= 16 && which <= 18) {   // 256x256 tiles on four waves, weights streamed into registers (gemm4wr.inc); 17: without its MFMAs (wrong results, valid timing)
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!gemm4wr_ok(p, true, std::is_same<TOut, bf16_t>::value)) {
-        omp_set_error("omp_gemm_bias_act: selector %d (register-streamed weights) takes row-major destinations of selector 9 with K %% 256 == 0", which);
-        return OMP_ERR_UNSUPPORTED;
-      }
-      const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-      const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-      int rc = OMP_OK;
-      if (which == 16) rc = launch_4wr<TOut>(p, st);
-      else if (which == 18) {   // development: per-workgroup phase timestamps (tools/gemm4wr_trace.py)
-        if (p.split_out || cx.gemm_trace == nullptr || (long long)ceil_div64(p.M, 256) * ceil_div64(p.N, 256) > cx.gemm_trace_cap) {
-          omp_set_error("omp_gemm_bias_act: selector 18 needs omp_debug_set_gemm_trace(buffer for every 256x256 tile) and a plain destination");
-          return OMP_ERR_INVALID;
-        }
-        p.trace = cx.gemm_trace;
-        rc = launch_4wr_t<TOut, false, 4>(p, st);
-      } else if constexpr (std::is_same<TOut, bf16_t>::value) {
-        if (p.split_out) { omp_set_error("omp_gemm_bias_act: selector 17 takes plain bf16 products"); return OMP_ERR_UNSUPPORTED; }
-        rc = launch_4wr_t<TOut, false, 3>(p, st);
-      } else {
-        omp_set_error("omp_gemm_bias_act: selector 17 takes plain bf16 products");
-        return OMP_ERR_UNSUPPORTED;
-      }
-      if (slot >= 0) omp_prof_end(pcls, slot, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selector %d (register-streamed weights) is bf16-only", which);
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which == 20 || which == 21) {   // persistent 256x256 tiles on four waves, register-only epilogue (gemm4wp.inc); 21: 2/3 of its operand bytes (wrong results, valid timing)
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!gemm4wp_ok(p, true, std::is_same<TOut, bf16_t>::value)) {
-        omp_set_error("omp_gemm_bias_act: selector 20 (persistent four-wave tiles) takes row-major destinations with M, N, K multiples of 256 and 16-byte aligned bias / rows");
-        return OMP_ERR_UNSUPPORTED;
-      }
-      const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-      const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-      int rc = OMP_OK;
-      if (which == 20) rc = launch_4wp<TOut>(p, st);
-      else if constexpr (!std::is_same<TOut, bf16_t>::value) rc = launch_4wp_t<TOut, false, 5>(p, st);
-      else { omp_set_error("omp_gemm_bias_act: selector 21 takes fp32 destinations"); return OMP_ERR_UNSUPPORTED; }
-      if (slot >= 0) omp_prof_end(pcls, slot, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selector 20 (persistent four-wave tiles) is bf16-only");
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which == 22) {          // bf16x3: the three products fused over shared operand tiles (gemm4wp.inc, X3)
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!gemm4wx3_ok(p, true, std::is_same<TOut, bf16_t>::value)) {
-        omp_set_error("omp_gemm_bias_act: selector 22 takes bf16x3 operands (a_wrap = 2 K0, K = 3 K0, K0 %% 128 == 0), M and N multiples of 256, fp32 or split destination");
-        return OMP_ERR_UNSUPPORTED;
-      }
-      const int pcls = p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC;
-      const int slot = omp_prof_active(pcls) ? omp_prof_begin(pcls, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut))) : -1;
-      int rc = launch_4wx3<TOut>(p, st);
-      if (slot >= 0) omp_prof_end(pcls, slot, st);
-      if (rc != OMP_OK) return rc;
-    } else {
-      omp_set_error("omp_gemm_bias_act: selector 22 is bf16-only");
-      return OMP_ERR_UNSUPPORTED;
-    }
-  } else if (which == 15) {          // development: gemm_dma<128,128,2> with per-workgroup phase timestamps
-    p.tiles_m = (int)ceil_div64(p.M, 128); p.tiles_n = (int)ceil_div64(p.N, 128);
-    if (cx.gemm_trace == nullptr || (long long)p.tiles_m * p.tiles_n > cx.gemm_trace_cap) {
-      omp_set_error("omp_gemm_bias_act: selector 15 needs omp_debug_set_gemm_trace(buffer for >= %d workgroups)", p.tiles_m * p.tiles_n);
+  if (!gemm_accepts(*sel, p, BI, BO)) return OMP_ERR_UNSUPPORTED;
+  // omp_debug_gemm_choice: the dispatch table is host logic, testable without a GPU
+  if (cx.gemm_choice_only) { cx.gemm_last_choice = which; return OMP_OK; }
+  if (sel->trace_tile > 0) {   // a launch-time condition: the choice-only call answers 15 / 18 without a buffer
+    const long long tiles = (long long)ceil_div64(p.M, sel->trace_tile) * ceil_div64(p.N, sel->trace_tile);
+    if (cx.gemm_trace == nullptr || tiles > cx.gemm_trace_cap || (which == 18 && p.split_out)) {
+      omp_set_error("omp_gemm_bias_act: selector %d needs omp_debug_set_gemm_trace(buffer for >= %lld workgroups)%s", which, tiles, which == 18 ? " and a plain destination" : "");
       return OMP_ERR_INVALID;
     }
     p.trace = cx.gemm_trace;
-    int rc = launch_dma<T, TOut, 128, 128, 2, true>(p, st);
-    if (rc != OMP_OK) return rc;
-  } else if (which == 3) {
-    dim3 grid((unsigned)ceil_div64(p.N, 64), (unsigned)ceil_div64(p.M, 16));
-    hipLaunchKernelGGL((gemm_rows<T, TOut>), grid, dim3(256), 0, st, p);
-  } else {
-    omp_set_error("omp_gemm_bias_act: unknown kernel selector %d", which);
-    return OMP_ERR_INVALID;
   }
+  if (which == 4) return launch_small<T, TOut>(p, st);   // checks its own launch: the few-row decoder step pays for every host call
+  int rc;
+  {
+    // bench.py's matrix-core roofline legs: hipEvent bracket + flop count of the large-M GEMMs
+    OmpProfScope prof(!sel->prof ? -1 : p.M >= 32768 ? OMP_PROF_GEMM : OMP_PROF_GEMM_DEC, st, 2.0 * (double)p.M * p.N * p.K, gemm_alg_bytes(p, sizeof(T), sizeof(TOut)));
+    rc = gemm_launch_sel<T, TOut>(which, p, st);
+  }
+  if (rc != OMP_OK) return rc;
   OMP_CHECK_LAUNCH("omp_gemm_bias_act");
   return OMP_OK;
 }

@@ -350,15 +350,8 @@ __global__ __launch_bounds__(512, 2) void gemm_256(GemmP p) {
 template <typename TOut, int SM, bool SPLIT = false>
 int launch_256_sm(GemmP& p, hipStream_t st) {
   constexpr size_t smem = 8 * 64 * 68 * 4;   // 139264 B: the epilogue regions; the two operand buffers take 131072 B
-  auto kern = gemm_256<TOut, SM, SPLIT>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = gemm_256<TOut, SM, SPLIT>;
+  if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   p.tiles_m = (int)ceil_div64(p.M, 256); p.tiles_n = (int)ceil_div64(p.N, 256);
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(512), smem, st, p);
   return OMP_OK;

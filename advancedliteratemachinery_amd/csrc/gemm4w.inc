@@ -393,15 +393,8 @@ template <typename TOut, int SM, bool SPLIT, int NS, int ABL = 0>
 int launch_4w_sm(GemmP& p, hipStream_t st) {
   constexpr size_t ring = (size_t)NS * 32768, epi = 4 * 64 * 132 * 4;   // 5 operand-tile slots; the epilogue regions alias them
   constexpr size_t smem = ring > epi ? ring : epi;
-  auto kern = gemm_4w<TOut, SM, SPLIT, NS, ABL>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = gemm_4w<TOut, SM, SPLIT, NS, ABL>;
+  if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   p.tiles_m = (int)ceil_div64(p.M, 256); p.tiles_n = (int)ceil_div64(p.N, 256);
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(256), smem, st, p);
   return OMP_OK;

@@ -375,33 +375,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the requests behind the last tile
 }
 
-inline int gemm_cu_count() {   // CU count of the current device (per-device cache; a lost race repeats an idempotent query)
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  int v = cus[dev].load(std::memory_order_relaxed);
-  if (v == 0) {
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cus[dev].store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-
 template <typename TOut, bool SPLIT, int ABL = 0, bool X3 = false>
 int launch_4wp_t(GemmP& p, hipStream_t st) {
   constexpr size_t smem = 5 * 32768;   // the X ring (X3: four of the five slots)
-  auto kern = gemm_4w_p<TOut, SPLIT, ABL, X3>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = gemm_4w_p<TOut, SPLIT, ABL, X3>;
+  if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   p.tiles_m = (int)ceil_div64(p.M, 256); p.tiles_n = (int)ceil_div64(p.N, 256);
   const int ntile = p.tiles_m * p.tiles_n;
-  int grid = gemm_cu_count() & ~7;     // a multiple of 8: a workgroup's tiles stay on its XCD's share of the tile list
+  int grid = omp_device_cus() & ~7;    // a multiple of 8: a workgroup's tiles stay on its XCD's share of the tile list
   if (grid < 8) grid = 8;
   if (grid > ntile) grid = ntile;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, p);

@@ -309,15 +309,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 template <typename TOut, bool SPLIT, int ABL = 0>
 int launch_4wr_t(GemmP& p, hipStream_t st) {
   constexpr size_t smem = 5 * 32768;   // the X ring; the epilogue regions (4 x 17 KB) alias it
-  auto kern = gemm_4w_r<TOut, SPLIT, ABL>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_gemm_bias_act: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = gemm_4w_r<TOut, SPLIT, ABL>;
+  if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   p.tiles_m = (int)ceil_div64(p.M, 256); p.tiles_n = (int)ceil_div64(p.N, 256);
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(256), smem, st, p);
   return OMP_OK;

@@ -203,15 +203,8 @@ __global__ __launch_bounds__(NW * 64) void kv_rows_kernel(KvP p) {
 template <bool SWAP>
 int launch_kv(const KvP& p, hipStream_t st) {
   const size_t smem = (size_t)RT * A_PITCH + TILE_SLACK;
-  auto kern = kv_rows_kernel<SWAP>;
-  static bool done = false;   // per instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_kv_project_rows: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = kv_rows_kernel<SWAP>;
+  if (const int rc = omp_raise_lds<kern>("omp_kv_project_rows")) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.rows / RT)), dim3(NW * 64), smem, st, p);
   OMP_CHECK_LAUNCH("omp_kv_project_rows");
   return OMP_OK;
@@ -233,8 +226,6 @@ extern "C" int omp_kv_project_rows(const void* rows, const void* wstream, int64_
   hipStream_t st = (hipStream_t)s;
   const double fl = 2.0 * (double)p.rows * D * D * n_slabs;
   const double by = (double)p.rows * D * 2 + (double)p.rows * D * n_slabs * 2 + (double)n_slabs * D * D * 2;
-  const int slot = omp_prof_active(OMP_PROF_GEMM) ? omp_prof_begin(OMP_PROF_GEMM, st, fl, by) : -1;
-  const int rc = vt ? launch_kv<true>(p, st) : launch_kv<false>(p, st);
-  if (slot >= 0) omp_prof_end(OMP_PROF_GEMM, slot, st);
-  return rc;
+  OmpProfScope prof(OMP_PROF_GEMM, st, fl, by);
+  return vt ? launch_kv<true>(p, st) : launch_kv<false>(p, st);
 }

@@ -308,15 +308,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void mlp_fused_kernel(MlpP p) {
 template <typename TX, int C, int RG, int NW, int NS, int WPS, bool TRACE = false>
 int launch_mlp_t(const MlpP& p, hipStream_t st) {
   constexpr size_t smem = (size_t)NS * (C * 128 + 1024);
-  auto kern = mlp_fused_kernel<TX, C, RG, NW, NS, WPS, TRACE>;
-  static bool done = false;   // per template instantiation
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_swin_mlp_fused: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = mlp_fused_kernel<TX, C, RG, NW, NS, WPS, TRACE>;
+  if (const int rc = omp_raise_lds<kern>("omp_swin_mlp_fused")) return rc;
   const int64_t rows_per_wg = (int64_t)NW * RG * 16;
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div64(p.M, rows_per_wg)), dim3(64 * NW), smem, st, p);
   OMP_CHECK_LAUNCH("omp_swin_mlp_fused");
@@ -368,10 +361,8 @@ extern "C" int omp_swin_mlp_fused2(const void* x, int x_dtype, int64_t ldx, cons
   p.M = M; p.nsub = hidden / 32; p.trace = omp_cur().mlp_trace;
   hipStream_t st = (hipStream_t)s;
   const int v = omp_cur().mlp_variant;
-  const int slot = omp_prof_active(OMP_PROF_MLP) ? omp_prof_begin(OMP_PROF_MLP, st, 4.0 * (double)M * C * hidden, (x_dtype == OMP_F32 ? 8.0 : 4.0) * (double)M * C + (double)(hidden / 32) * (C * 128 + 1024)) : -1;
-  const int rc = dispatch_mlp(p, C, v, st);
-  if (slot >= 0) omp_prof_end(OMP_PROF_MLP, slot, st);
-  return rc;
+  OmpProfScope prof(OMP_PROF_MLP, st, 4.0 * (double)M * C * hidden, (x_dtype == OMP_F32 ? 8.0 : 4.0) * (double)M * C + (double)(hidden / 32) * (C * 128 + 1024));
+  return dispatch_mlp(p, C, v, st);
 }
 
 namespace {

@@ -34,10 +34,10 @@ int omp_prof_read_class(int cls, double* total_ms, int64_t* count, double* work)
 /* classes 1 and 2: summed algorithmic HBM bytes of the bracketed launches and the sum over launches of
  * max(flops / 2.5 PFLOP/s, bytes / 8 TB/s) -- the time they would take on their own rooflines */
 int omp_prof_read_roofline(int cls, double* bytes, double* roofline_seconds);
-/* GEMM kernel selector: 0 auto; 3 row-streaming; 4 split-K small-M; 5 / 6 DMA 128x128 / 64x64; 9 gemm_256; 10 (= 11) gemm_4w; 16 gemm_4w_r
- * (weights streamed into registers; K % 256 == 0); 20 gemm_4w_p (the same, persistent over tiles, register-only epilogue; M, N, K
- * multiples of 256); 22 its fused three-product instantiation for bf16x3 operands.  Wrong results, valid timing: 12..14 gemm_4w without DMA / fragment reads / MFMAs, 17 gemm_4w_r without MFMAs, 21
- * gemm_4w_p with 2/3 of its operand bytes.  Traces: 15 gemm_dma<128,128,2>, 18 gemm_4w_r (omp_debug_set_gemm_trace). */
+/* GEMM kernel selector: 0 = the measured default (csrc/gemm.hip: gemm_auto_select), else a row of csrc/gemm.hip: GEMM_SELECTORS -- the table
+ * names every selector, the products it takes and what it is for (12..14, 17, 21: ablations with wrong results and valid timing; 15, 18:
+ * traces, omp_debug_set_gemm_trace).  A selector that does not take a product is OMP_ERR_UNSUPPORTED; row statistics
+ * (OMP_STORE_ROWSTAT) and LayerNorm prologues run on the one kernel that has them whatever is forced. */
 int omp_debug_force_gemm_kernel(int which);
 /* the selector omp_gemm_bias_act would take for these arguments (no launch, no device access: host logic, tests/test_host_logic.py);
  * < 0: the error code of its argument checks.  Like every hook of this header it acts on the calling thread's current context: do not

@@ -15,7 +15,6 @@
 // needs no cross-lane traffic; K and V of the window/head are staged once in LDS (fp32) and read
 // as wave-wide broadcasts (conflict-free ds_read_b128).
 #include "common.h"
-#include <atomic>
 
 namespace {
 
@@ -777,20 +776,6 @@ extern "C" int omp_swin_expand_bias(const float* rel_bias_table, int nH, float* 
   return OMP_OK;
 }
 
-namespace {
-int device_cus() {   // compute units of the current device (cached per device)
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  int v = cus[dev].load(std::memory_order_relaxed);
-  if (v == 0) {
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cus[dev].store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-}  // namespace
-
 extern "C" int omp_swin_window_attn(const void* qkv, const float* qkv_bias, const float* rel_bias_table,
                                     void* out, int dtype, int B, int H, int W, int C, int nH, int window,
                                     int shift, omp_stream_t s) {
@@ -818,7 +803,7 @@ extern "C" int omp_swin_window_attn2(const void* qkv, const float* qkv_bias, con
   dim3 pgrid = grid;
   {
     const int per_cu = 2;
-    const int64_t co = (int64_t)device_cus() * per_cu / grid.y;
+    const int64_t co = (int64_t)omp_device_cus() * per_cu / grid.y;
     if (co >= 1 && co < (int64_t)grid.x) pgrid.x = (unsigned)co;
   }
   if (swin_impl == 1) {

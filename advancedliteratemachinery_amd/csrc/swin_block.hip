@@ -24,7 +24,6 @@
 //     the residual / proj-weight loads are never drained at a barrier
 // Measured (profiles/r03o_kbench_swin_block.txt): 32 images of 256 x 256 tokens, 2.26 ms for the four launches -> 1.11 ms;
 // instruction-issue-bound (about 2 900 instructions per wave and window), HBM floor 0.36 ms.
-#include <atomic>
 
 #include "common.h"
 
@@ -757,31 +756,7 @@ __global__ __launch_bounds__(512, 1) void swin_block256_kernel(SwinBlock256P p) 
 
 }  // namespace
 
-// Per-device launch state, safe under concurrent pipeline lanes: the CU count of the CURRENT device and "dynamic LDS
-// limit raised" flags, in atomics indexed by device ordinal.  A lost race only repeats an idempotent query / attribute call.
 namespace {
-constexpr int MAX_DEVS = 64;
-inline int current_device_cus(int* dev_out) {
-  static std::atomic<int> cus[MAX_DEVS];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVS) return -1;
-  *dev_out = dev;
-  int v = cus[dev].load(std::memory_order_relaxed);
-  if (v == 0) {
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cus[dev].store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-template <typename K>
-inline bool raise_lds_limit_once(std::atomic<bool>* done, int dev, K kern_a, K kern_b) {
-  if (done[dev].load(std::memory_order_acquire)) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern_a), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern_b), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return false;
-  done[dev].store(true, std::memory_order_release);
-  return true;
-}
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
@@ -805,16 +780,11 @@ extern "C" int omp_swin_attn_block(const void* x, void* out, const float* ln_g, 
   p.n_win = (int)nw;
   OMP_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(qkv_w) && aligned16(proj_w) && aligned16(bias_expanded),
                 "omp_swin_attn_block: x / out / qkv_w / proj_w / bias_expanded must be 16-byte aligned (the kernel moves 16-byte vectors)");
-  int dev = 0;
-  const int n_cu = current_device_cus(&dev);
-  static std::atomic<bool> lds_done[MAX_DEVS];
-  if (n_cu <= 0 || !raise_lds_limit_once(lds_done, dev, swin_block_kernel<false>, swin_block_kernel<true>)) {
-    omp_set_error("omp_swin_attn_block: cannot query the device / raise the dynamic LDS limit");
-    return OMP_ERR_LAUNCH;
-  }
+  p.trace = omp_cur().mlp_trace;   // omp_debug_swin_mlp_trace: the development buffer also takes this kernel's phase sums
+  if (const int rc = p.trace == nullptr ? omp_raise_lds<swin_block_kernel<false>>("omp_swin_attn_block") : omp_raise_lds<swin_block_kernel<true>>("omp_swin_attn_block")) return rc;
+  const int n_cu = omp_device_cus();
   const int pairs = (int)((nw + 1) / 2);
   const int grid = pairs < n_cu ? pairs : n_cu;
-  p.trace = omp_cur().mlp_trace;   // omp_debug_swin_mlp_trace: the development buffer also takes this kernel's phase sums
   if (p.trace != nullptr) hipLaunchKernelGGL(swin_block_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_BYTES, (hipStream_t)s, p);
   else hipLaunchKernelGGL(swin_block_kernel<false>, dim3((unsigned)grid), dim3(512), LDS_BYTES, (hipStream_t)s, p);
   OMP_CHECK_LAUNCH("omp_swin_attn_block");
@@ -840,12 +810,7 @@ extern "C" int omp_swin_attn_block_packed(const void* x, void* out, const float*
   p.n_win = (int)nw;
   OMP_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(wpack) && aligned16(bias_expanded),
                 "omp_swin_attn_block_packed: x / out / wpack / bias_expanded must be 16-byte aligned (the kernel moves 16-byte vectors)");
-  int dev = 0;
-  const int n_cu = current_device_cus(&dev);
-  if (n_cu <= 0) {
-    omp_set_error("omp_swin_attn_block_packed: cannot query the device");
-    return OMP_ERR_LAUNCH;
-  }
+  const int n_cu = omp_device_cus();
   const int grid = (int)(nw < n_cu ? nw : n_cu);
   p.trace = omp_cur().mlp_trace;
   if (p.trace != nullptr) hipLaunchKernelGGL(swin_block256_kernel<true>, dim3((unsigned)grid), dim3(512), LDS2_BYTES, (hipStream_t)s, p);

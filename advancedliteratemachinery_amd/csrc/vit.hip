@@ -452,15 +452,8 @@ extern "C" int omp_vit_attn(const void* q, int64_t ldq, const void* K, const voi
   }
   constexpr int NB = 18;
   constexpr size_t smem = 2 * (size_t)NB * 16 * 128;
-  auto kern = vit_attn_kernel<NB>;
-  static bool done = false;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_vit_attn: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = vit_attn_kernel<NB>;
+  if (const int rc = omp_raise_lds<kern>("omp_vit_attn")) return rc;
   hipLaunchKernelGGL(kern, dim3(nH, B), dim3(256), smem, (hipStream_t)s, (const bf16_t*)q, ldq, (const bf16_t*)K,
                      (const bf16_t*)Vt, (bf16_t*)out, ldo, T, nH);
   OMP_CHECK_LAUNCH("omp_vit_attn");
@@ -477,15 +470,8 @@ extern "C" int omp_vit_attn_qkv(const void* qkv, int64_t ld, void* out, int64_t 
   }
   constexpr int NB = 18;
   constexpr size_t smem = 2 * (size_t)NB * 16 * 128;
-  auto kern = vit_attn_kernel<NB, true>;
-  static bool done = false;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      omp_set_error("omp_vit_attn_qkv: cannot raise dynamic LDS limit");
-      return OMP_ERR_LAUNCH;
-    }
-    done = true;
-  }
+  constexpr auto kern = vit_attn_kernel<NB, true>;
+  if (const int rc = omp_raise_lds<kern>("omp_vit_attn_qkv")) return rc;
   const bf16_t* q = reinterpret_cast<const bf16_t*>(qkv);
   hipLaunchKernelGGL(kern, dim3(nH, B), dim3(256), smem, (hipStream_t)s, q, ld, q + nH * 64, q + 2 * nH * 64, (bf16_t*)out, ldo, T, nH);
   OMP_CHECK_LAUNCH("omp_vit_attn_qkv");
@@ -500,12 +486,9 @@ static int launch_a3(const float* sel, int ld_sel, const void* feat, float* pool
   const T* f = reinterpret_cast<const T*>(feat);
 #define A3_LAUNCH(CPT)                                                                                              \
   do {                                                                                                              \
-    auto kern = a3_pool_kernel<T, CPT>;                                                                             \
-    if (smem > 48 * 1024 &&                                                                                         \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                            160 * 1024) != hipSuccess) {                                                            \
-      omp_set_error("omp_a3_pool: cannot raise dynamic LDS limit");                                                 \
-      return OMP_ERR_LAUNCH;                                                                                        \
+    constexpr auto kern = a3_pool_kernel<T, CPT>;                                                                   \
+    if (smem > 48 * 1024) {                                                                                         \
+      if (const int rc = omp_raise_lds<kern>("omp_a3_pool")) return rc;                                             \
     }                                                                                                               \
     hipLaunchKernelGGL(kern, dim3(B), dim3(256), smem, st, sel, ld_sel, f, pooled, attn, Tk, S, C);                 \
   } while (0)

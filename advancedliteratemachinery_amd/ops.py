@@ -100,7 +100,8 @@ def gemm_choice(M, N, K, dtype=OMP_BF16, out_dtype=None, act=ACT_NONE, residual=
                 lda=None, ldw=None, ldc=None, two_destinations=False, ln=False, small_m=False, base=1 << 20):
     """Host logic only (no device, no launch): the kernel selector omp_gemm_bias_act would take for a product of this shape -- the
     dispatch table of csrc/gemm.hip as a function (tests/test_host_logic.py pins it).  Pointers are synthetic, 4 KB-aligned addresses:
-    the library only tests them for null and alignment.  Returns the selector (csrc/omp355_debug.h) or raises on an argument error."""
+    the library only tests them for null and alignment.  Returns the selector (a row of
+    csrc/gemm.hip: GEMM_SELECTORS) or raises on an argument error."""
     out_dtype = dtype if out_dtype is None else out_dtype
     a = _lib.GemmArgs()
     split = out_dtype == OMP_BF16X2

@@ -292,6 +292,7 @@ def check_gemm_row_stats():
     the same product written as fp32 logits, then omp_row_argmax_prob -- on ragged shapes: ids identical (the product bits are the same; ties go to
     the lowest index in both), probabilities within 2e-6 relative (a different summation order of the exponentials).  Engines: bf16 operands, fp32
     operands, and the bf16x3 form (split-pair rows against the [hi | hi | lo] weight image)."""
+    from advancedliteratemachinery_amd import _lib
     out = []
     for (M, N, K) in ((300, 50257, 768), (129, 1104, 512), (64, 128, 256), (1000, 30522, 768)):
         A, W, b = rnd(M, K, seed=M + 1), rnd(N, K, seed=N + 2) / K ** 0.5, rnd(N, seed=N + 3, scale=0.2)
@@ -318,6 +319,24 @@ def check_gemm_row_stats():
                 out.append(rec('gemm_row_stats[%s %dx%dx%d] tie %d = %d in the ragged last tile: ids identical' % (tag, M, N, K, t0 + 2, N - 1),
                                float((i0 != i1).sum()), 0))
                 out.append(rec('gemm_row_stats[%s %dx%dx%d] ... and the lower index wins' % (tag, M, N, K), float((i1 != t0 + 2).sum()) if tag == 'fp32' else 0.0, 0))
+            if M <= 64:
+                # with the split-K small-M kernel forced (selector 4) a ROWSTAT product used to write [M, N] logits into the
+                # [M][2 ceil(N / 128)][4] buffer; the row statistics now go to the 128x128 kernel whatever is forced -- the same records as
+                # under selector 0, and the words behind the buffer stay untouched
+                nt = 2 * ((N + 127) // 128)
+                stats = {}
+                for which in (0, 4):
+                    buf = torch.full((M * nt * 4 + 1024,), -77.0, dtype=torch.float32, device=DEV)
+                    ops.force_gemm_kernel(which)
+                    try:
+                        ops.gemm(Ad, Wd, bd, out=buf[:M * nt * 4].view(M, nt, 4), out_dtype=torch.float32, store_mode=_lib.STORE_ROWSTAT, ldc=N)
+                    finally:
+                        ops.force_gemm_kernel(0)
+                    stats[which] = buf.cpu()
+                out.append(rec('gemm_row_stats[%s %dx%dx%d] forced selector 4: the records of selector 0' % (tag, M, N, K),
+                               float((stats[4][:M * nt * 4] != stats[0][:M * nt * 4]).sum()), 0))
+                out.append(rec('gemm_row_stats[%s %dx%dx%d] forced selector 4: guard words behind the buffer untouched' % (tag, M, N, K),
+                               float((stats[4][M * nt * 4:] != -77.0).sum()), 0))
         # bf16x3: split-pair activation rows against the [hi | hi | lo] image of the fp32 weight
         As, W3, bd = ops.split_bf16(A.to(DEV)), ops.split_weight3(W.to(DEV)), b.to(DEV)
         lg = ops.gemm(As, W3, bd, out_dtype=torch.float32, a_wrap=2 * K)

@@ -639,6 +639,27 @@ def test_gemm_dispatch_table():
         G(128, 512, 100)
 
 
+def test_gemm_choice_grid_matches_the_record():
+    """The whole dispatch table of csrc/gemm.hip (GEMM_SELECTORS, gemm_auto_select, gemm_accepts and the argument checks in front of them) replayed
+    over the grid of tools/gemm_choice_grid.py -- every forced selector x dtype pair x store mode, 8.3 M cells in 304 blocks -- against
+    tests/golden/gemm_choice_grid.json: per block the SHA-256 of the answer vector (selector or negative error code) and its histogram.  A host
+    refactor of launch_gemm must leave every block as recorded; a rule that changes on purpose regenerates exactly its blocks
+    (`python tools/gemm_choice_grid.py --print BLOCK` lists a block cell by cell)."""
+    import importlib.util
+    import json
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('gemm_choice_grid', os.path.join(ROOT, 'tools', 'gemm_choice_grid.py'))
+    grid = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(grid)
+    with open(os.path.join(ROOT, 'tests', 'golden', 'gemm_choice_grid.json')) as f:
+        want = json.load(f)
+    got = grid.record()
+    assert sorted(got) == sorted(want['blocks']) and len(got) == 304
+    assert sum(sum(b['hist'].values()) for b in got.values()) == want['cells'] == 8273664
+    bad = {k: (want['blocks'][k]['hist'], got[k]['hist']) for k in got if got[k] != want['blocks'][k]}
+    assert not bad, 'blocks that differ from the record (recorded histogram, histogram now): %r' % bad
+
+
 def test_gemm_choice_refuses_what_the_launch_path_refuses():
     """omp_debug_gemm_choice used to return BEFORE the selector / argument compatibility checks of launch_gemm, so the host-logic
     test of the dispatch table could report a selector for arguments the real call rejects.  A forced selector that does not take the
