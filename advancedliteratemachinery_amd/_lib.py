@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libomp355.so')
 
 OMP_F32, OMP_BF16, OMP_BF16X2 = 0, 1, 2   # BF16X2: split-bf16 pair rows [hi | lo] (include/omp355.h)
-ABI_VERSION = 23
+ABI_VERSION = 24
 STORE_PLAIN, STORE_KBLK, STORE_VBLK, STORE_ROWSTAT = 0, 2, 3, 4
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 DEC_PT, DEC_POLY, DEC_REC = 0, 1, 2
@@ -141,6 +141,7 @@ _SIGS = {
                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'omp_polygon_rectify': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
     'omp_resize_crops': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'omp_lexicon_nearest': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'omp_ctx_create': (c_int, [ctypes.POINTER(c_void_p)]),
     'omp_ctx_destroy': (c_int, [c_void_p]),
     'omp_ctx_make_current': (c_int, [c_void_p]),

@@ -104,12 +104,18 @@ def predict_raw(model, images, args, orig_sizes=None, ragged=False):
 
 
 @torch.no_grad()
-def predict(model, images, args, targets=None, orig_sizes=None, ragged=False):
+def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
     Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
     ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
     others in the call.  ragged=True: every image is decoded exactly as if it had been submitted alone; without targets its
-    orig_size is its own (h, w), not the padded batch's."""
+    orig_size is its own (h, w), not the padded batch's.
+    lexicon: a utils.lexicon.LexiconMatcher, a list of words shared by all images, or a list of word lists, one per image
+    (a raw list is encoded with args.chars and uploaded for this call; pass a matcher to keep it on the device).  Every record
+    then gains `lex` (the nearest word, or None when lexicon_max_dist / lexicon_max_ratio reject it), `lex_index` and
+    `lex_dist`, from its `rec`, which stays as it is; all words of the call are matched in one device call."""
+    if lexicon is not None and args.infer_vie:
+        raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     if orig_sizes is None and targets is not None and args.infer_vie:
         orig_sizes = [t['orig_size'] for t in targets]
     raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged)
@@ -124,17 +130,25 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False):
                {'file_name': str(b), 'orig_size': nt[b] if ragged else (nt.tensors.shape[2], nt.tensors.shape[3])})
         seq_cpu = [t[0].cpu() for t in r[0]]
         out.append(decode_pred_seq(seq_cpu, r[1][0].cpu(), tgt, args))
+    if lexicon is not None:
+        from ..utils import lexicon as LX
+        matcher = LX.resolve_lexicon(lexicon, len(out), next(model.parameters()).device, args.chars)
+        LX.annotate_records(out, matcher, 'rec', 'lex', lexicon_max_dist, lexicon_max_ratio)
     return out
 
 
 @torch.no_grad()
-def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False):
+def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
+                   lexicon_max_ratio=None):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
     ragged=True: the preprocessed images are decoded at their own sizes (predict), not padded to the largest of the call.
+    lexicon, lexicon_max_dist, lexicon_max_ratio: as predict (records gain `lex`, `lex_index`, `lex_dist`).
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
+    if lexicon is not None and args.infer_vie:
+        raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     dev = next(model.parameters()).device
     if preprocessor is None:
         preprocessor = DevicePreprocessor(args.test_min_size, args.test_max_size, dev)
@@ -142,7 +156,8 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     nt, _ = preprocessor(imgs)
     targets = [{'file_name': (file_names[b] if file_names is not None else str(b)),
                 'orig_size': (int(im.shape[0]), int(im.shape[1]))} for b, im in enumerate(imgs)]
-    return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged), preprocessor
+    return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged, lexicon=lexicon,
+                   lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio), preprocessor
 
 
 def _meta(t):

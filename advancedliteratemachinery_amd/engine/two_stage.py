@@ -52,7 +52,8 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 
 
 @torch.no_grad()
-def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False):
+def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
+                       lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -60,12 +61,23 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     reference tree).  crop='box' reads the bounding box of each polygon; crop='polygon' reads the word rectified along
     its polygon (rotated, vertical and curved text arrives upright and tight; `resizer` is then a PolygonCropper) and the
     records gain `crop`: 'polygon' and `strip`: (sh, sw), the rectified word's own size.  `ragged` goes to predict_images.
+    lexicon (a utils.lexicon.LexiconMatcher, a list of words, or a list of word lists, one per image), lexicon_max_dist,
+    lexicon_max_ratio: records gain `lex`, `lex_index`, `lex_dist` from `rec` (predict_images) and `mgp_lex`, `mgp_lex_index`,
+    `mgp_lex_dist` from `mgp_text`; a raw list is encoded with args.chars for the one and MGP-STR's character set for the
+    other, a matcher serves both with its own alphabet.  One device call per source string for all words of all images.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
+    if lexicon is not None and args.infer_vie:
+        raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
-    records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor, ragged=ragged)
+    if lexicon is not None:
+        from ..utils import lexicon as LX
+        if not LX.is_matcher(lexicon):
+            lexicon = [list(w) if not isinstance(w, str) else w for w in lexicon]   # read a generator once, use it twice
+    records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor, ragged=ragged,
+                                           lexicon=lexicon, lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio)
     boxes, polys, owner = [], [], []
     for b, recs in enumerate(records):
         h, w = int(imgs[b].shape[0]), int(imgs[b].shape[1])
@@ -80,4 +92,8 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     for r, m in zip(owner, reads):
         r['mgp_text'], r['mgp_conf'], r['mgp_choice'] = m['char_text'], m['conf'], m['choice']
         r['mgp_ids'] = dict(char=m['char_ids'], bpe=m['bpe_ids'], wp=m['wp_ids'])
+    if lexicon is not None:
+        from ..model.mgp_str import CHARACTER
+        matcher = LX.resolve_lexicon(lexicon, len(records), dev, CHARACTER)
+        LX.annotate_records(records, matcher, 'mgp_text', 'mgp_lex', lexicon_max_dist, lexicon_max_ratio)
     return records, preprocessor, resizer

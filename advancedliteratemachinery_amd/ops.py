@@ -635,3 +635,25 @@ def swin_rows_block(x, att, wstream, wave_stride, proj_b, n2, fc1_b, fc2_b, next
         qkv = None
     _lib.check(_lib.lib().omp_swin_rows_block(ctypes.byref(a), stream()), 'omp_swin_rows_block')
     return qkv
+
+
+def lexicon_nearest(q_codes, q_len, q_lo, q_hi, pool, pool_bytes, offsets, L, best=None, range_hint=0):
+    """omp_lexicon_nearest (csrc/lexicon.hip; operands as utils/lexicon.py packs them): q_codes uint8 [N, 64], q_len / q_lo /
+    q_hi int32 [N] (q_lo and q_hi both None: the whole lexicon), pool uint8 with pool_bytes valid bytes, offsets int32 [L + 1]
+    -> best int64 [N] holding the uint64 keys (dist << 32) | idx, all ones = no word."""
+    N = q_len.numel()
+    for name, t, dtype, numel in (('q_codes', q_codes, torch.uint8, N * 64), ('q_len', q_len, torch.int32, N), ('q_lo', q_lo, torch.int32, N),
+                                  ('q_hi', q_hi, torch.int32, N), ('pool', pool, torch.uint8, pool_bytes), ('offsets', offsets, torch.int32, L + 1)):
+        if t is None:
+            continue
+        _c(t, name)
+        if t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be %s with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if best is None:
+        best = torch.empty(N, dtype=torch.int64, device=q_len.device)
+    elif best.dtype != torch.int64 or best.numel() < N or not best.is_contiguous():
+        raise ValueError('best must be a contiguous int64 tensor with at least %d elements' % N)
+    rc = _lib.lib().omp_lexicon_nearest(ptr(q_codes), ptr(q_len), ptr(q_lo), ptr(q_hi), N, ptr(pool), pool_bytes, ptr(offsets), L,
+                                        int(range_hint), ptr(best), stream())
+    _lib.check(rc, 'omp_lexicon_nearest')
+    return best

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OMP_ABI_VERSION 23
+#define OMP_ABI_VERSION 24
 #define OMP_MAX_DEC_LAYERS 8
 
 enum { OMP_OK = 0, OMP_ERR_LAUNCH = -5, OMP_ERR_INVALID = -22, OMP_ERR_UNSUPPORTED = -95 };
@@ -593,6 +593,28 @@ int omp_polygon_rectify(const omp_rectify_desc* desc, int n, int64_t total_tiles
  * points to in ONE packed int32 table, then lut (float [3][256]).  dst: fp32 [n, 3, out_h, out_w].  One launch. */
 int omp_resize_crops(const omp_resize_desc* desc, int n, const int32_t* table, int64_t table_len, const float* lut,
                      float* dst, int out_h, int out_w, omp_stream_t s);
+
+/* ---- lexicon correction: the nearest dictionary word of every query -------------
+ * Plain Levenshtein distance (insert / delete / substitute cost 1, no transpositions): the distance the reference's
+ * recogniser evaluation is built on (OCR/MGP-STR/test_final.py:14, nltk.metrics.distance.edit_distance).  The glue
+ * between a reader and a word list ships with neither reference project; utils/lexicon.py holds the specification
+ * (edit_distance_cpu, nearest_cpu) and packs the operands:
+ *   q_codes  uint8 [n][64]: the queries as alphabet indices; 254 = a character outside the alphabet
+ *   q_len    int32 [n]: characters per query, 0..64.  A length outside that range is REFUSED on the device: best[q] = all ones
+ *   q_lo, q_hi  int32 [n] each, or both NULL: query q searches the lexicon indices [q_lo[q], q_hi[q]), CLAMPED on the
+ *            device to [0, L]; NULL = the whole lexicon
+ *   pool     uint8 [pool_bytes]: the lexicon's words back to back as alphabet indices; 255 = a character outside the
+ *            alphabet (254 and 255 match nothing, each other included)
+ *   offsets  int32 [L + 1]: word i is pool[offsets[i] .. offsets[i + 1]), at most 255 characters; entries are clamped
+ *            into the pool on the device, so no table can make the kernel read outside pool[0 .. pool_bytes)
+ *   range_hint  the longest range of the call if the caller knows it, else 0: sizes the grid only, never the result
+ *   best     uint64 [n], written by this call (a fill launch ahead of the search launch on the same stream; the caller
+ *            initialises nothing): (dist << 32) | index of the nearest word of the range, the lowest index among equals;
+ *            all ones for an empty range or a refused query.
+ * Two launches (fill + search) whatever n and L; no allocation, no synchronisation. */
+int omp_lexicon_nearest(const uint8_t* q_codes, const int32_t* q_len, const int32_t* q_lo, const int32_t* q_hi, int n,
+                        const uint8_t* pool, int64_t pool_bytes, const int32_t* offsets, int L, int range_hint,
+                        uint64_t* best, omp_stream_t s);
 
 #ifdef __cplusplus
 }
