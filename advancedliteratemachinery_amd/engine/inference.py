@@ -81,17 +81,22 @@ def _ragged_inputs(images, dev):
 
 
 @torch.no_grad()
-def predict_raw(model, images, args, orig_sizes=None, ragged=False):
+def predict_raw(model, images, args, orig_sizes=None, ragged=False, windows=None, char_windows=None, clip_windows=False):
     """-> (per-image raw model outputs exactly as the reference's forward returns them, NestedTensor on the device).
     ragged=True: every image is decoded at its own size, no padding (OmniParser.infer(ragged=True)); the second value is then the
-    list of (h, w) per image, and the KIE default orig_size is each image's own size."""
+    list of (h, w) per image, and the KIE default orig_size is each image's own size.
+    windows, char_windows, clip_windows: window prompts, as OmniParser.infer takes them (every image's result then carries a third
+    entry, the window index per instance); without them the call is the plain one."""
     dev = next(model.parameters()).device
     seqs = build_prompts(args)
+    wkw = {}
+    if windows is not None or char_windows is not None:
+        wkw = dict(windows=windows, char_windows=char_windows, clip_windows=clip_windows)
     if ragged:
         img, mask, sizes = _ragged_inputs(images, dev)
         if args.infer_vie:
             seqs.append([torch.as_tensor(s) for s in (orig_sizes if orig_sizes is not None else sizes)])
-        return model.infer(img, mask, seqs, ragged=True), sizes
+        return model.infer(img, mask, seqs, ragged=True, **wkw), sizes
     nt = _as_nested(images)
     B = nt.tensors.shape[0]
     has_padding = bool(nt.mask.any())
@@ -100,11 +105,18 @@ def predict_raw(model, images, args, orig_sizes=None, ragged=False):
         if orig_sizes is None:
             orig_sizes = [(int(nt.tensors.shape[2]), int(nt.tensors.shape[3]))] * B
         seqs.append([torch.as_tensor(s) for s in orig_sizes])
-    return model.infer(nt.tensors, nt.mask, seqs, has_padding=has_padding), nt
+    return model.infer(nt.tensors, nt.mask, seqs, has_padding=has_padding, **wkw), nt
+
+
+def _n_images(images):
+    if hasattr(images, 'tensors'):
+        return int(images.tensors.shape[0])
+    return int(images.shape[0]) if isinstance(images, torch.Tensor) else len(images)
 
 
 @torch.no_grad()
-def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None):
+def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None,
+            windows=None, char_windows=None, clip_windows=False, grid=None):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
     Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
     ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
@@ -113,12 +125,26 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     lexicon: a utils.lexicon.LexiconMatcher, a list of words shared by all images, or a list of word lists, one per image
     (a raw list is encoded with args.chars and uploaded for this call; pass a matcher to keep it on the device).  Every record
     then gains `lex` (the nearest word, or None when lexicon_max_dist / lexicon_max_ratio reject it), `lex_index` and
-    `lex_dist`, from its `rec`, which stays as it is; all words of the call are matched in one device call."""
+    `lex_dist`, from its `rec`, which stays as it is; all words of the call are matched in one device call.
+    windows (a list of [x0, y0, x1, y1] in coordinate bins shared by all images, or one list per image), grid=(nx, ny) (shorthand
+    for utils.windows.grid_windows(nx, ny, args.num_bins)), char_windows, clip_windows: window prompts (OmniParser.infer; DESIGN.md
+    section 16) -- every window of an image is read under its own prompt in ONE engine call; an image's records are those of its
+    windows in window order, and every record gains `window` (the index) and `window_bins` (its [x0, y0, x1, y1]).  Without these
+    arguments the records are the plain call's.  Text spotting only; composes with ragged= and lexicon=."""
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     if orig_sizes is None and targets is not None and args.infer_vie:
         orig_sizes = [t['orig_size'] for t in targets]
-    raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged)
+    per_image = None
+    if windows is not None or grid is not None or char_windows is not None:
+        from ..utils import windows as WN
+        if args.infer_vie:
+            raise ValueError('windows= / grid= need text-spotting records; with args.infer_vie the engine returns entity tuples')
+        per_image = WN.resolve_windows(windows, _n_images(images), grid=grid, num_bins=args.num_bins)
+        if per_image is None:
+            per_image = WN.resolve_windows([WN.default_window(args)], _n_images(images))
+    wkw = {} if per_image is None else dict(windows=per_image, char_windows=char_windows, clip_windows=clip_windows)
+    raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged, **wkw)
     if args.infer_vie:
         return [r if r is not None else [] for r in raw]
     out = []
@@ -130,6 +156,9 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
                {'file_name': str(b), 'orig_size': nt[b] if ragged else (nt.tensors.shape[2], nt.tensors.shape[3])})
         seq_cpu = [t[0].cpu() for t in r[0]]
         out.append(decode_pred_seq(seq_cpu, r[1][0].cpu(), tgt, args))
+        if per_image is not None:
+            for rcd, w in zip(out[-1], r[2].tolist()):
+                rcd['window'], rcd['window_bins'] = int(w), list(per_image[b][w])
     if lexicon is not None:
         from ..utils import lexicon as LX
         matcher = LX.resolve_lexicon(lexicon, len(out), next(model.parameters()).device, args.chars)
@@ -139,12 +168,14 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
 
 @torch.no_grad()
 def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
-                   lexicon_max_ratio=None):
+                   lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
     ragged=True: the preprocessed images are decoded at their own sizes (predict), not padded to the largest of the call.
     lexicon, lexicon_max_dist, lexicon_max_ratio: as predict (records gain `lex`, `lex_index`, `lex_dist`).
+    windows, char_windows, clip_windows, grid: as predict (window prompts; records gain `window`, `window_bins`).  The bins of a
+    window are fractions of the RESIZED image the model sees, which is the original image scaled: the same fractions of both.
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
     if lexicon is not None and args.infer_vie:
@@ -157,7 +188,8 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     targets = [{'file_name': (file_names[b] if file_names is not None else str(b)),
                 'orig_size': (int(im.shape[0]), int(im.shape[1]))} for b, im in enumerate(imgs)]
     return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged, lexicon=lexicon,
-                   lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio), preprocessor
+                   lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio, windows=windows, char_windows=char_windows,
+                   clip_windows=clip_windows, grid=grid), preprocessor
 
 
 def _meta(t):

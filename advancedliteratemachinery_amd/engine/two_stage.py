@@ -53,7 +53,8 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 
 @torch.no_grad()
 def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
-                       lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None):
+                       lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
+                       grid=None):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -65,6 +66,9 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     lexicon_max_ratio: records gain `lex`, `lex_index`, `lex_dist` from `rec` (predict_images) and `mgp_lex`, `mgp_lex_index`,
     `mgp_lex_dist` from `mgp_text`; a raw list is encoded with args.chars for the one and MGP-STR's character set for the
     other, a matcher serves both with its own alphabet.  One device call per source string for all words of all images.
+    windows, char_windows, clip_windows, grid=(nx, ny): window prompts, as predict_images takes them: the
+    spotter reads every window of every image in one engine call, the records gain `window` and `window_bins`, and the recogniser
+    reads the crops of all windows' words exactly as it reads the plain call's.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
@@ -77,7 +81,8 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
         if not LX.is_matcher(lexicon):
             lexicon = [list(w) if not isinstance(w, str) else w for w in lexicon]   # read a generator once, use it twice
     records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor, ragged=ragged,
-                                           lexicon=lexicon, lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio)
+                                           lexicon=lexicon, lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio,
+                                           windows=windows, char_windows=char_windows, clip_windows=clip_windows, grid=grid)
     boxes, polys, owner = [], [], []
     for b, recs in enumerate(records):
         h, w = int(imgs[b].shape[0]), int(imgs[b].shape[1])

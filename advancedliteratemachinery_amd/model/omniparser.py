@@ -7,7 +7,9 @@ libomp355 (hand-written gfx950 kernels).  Additions over the reference:
     decoded exactly as if it had been submitted alone; `forward` then returns a list of B results;
   * `forced_instances`: fixed-length decoding for throughput measurement with random weights;
   * `infer(..., ragged=True)`: images of different sizes in one call, each encoded and decoded at its own size (no
-    padding anywhere) -- the reference's batch-1 answers with a batch's decode throughput.
+    padding anywhere) -- the reference's batch-1 answers with a batch's decode throughput;
+  * `infer(..., windows=...)`: window prompts -- several spatial (and first-character) windows per image decoded as rows of ONE
+    point phase over one encoder pass and one K/V projection.
 
 Return value per image (reference transformer.py:240-246,286):
   text spotting : ([pt (1,2N), poly (1,32N), rec (1,N,rec_length)] int64, [probs (N,rec_length)])
@@ -22,6 +24,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.env import env_flag, env_int
 from ..utils.nested_tensor import NestedTensor
+from ..utils import windows as WN
 from . import params
 from .backbone import Encoder
 from .transformer import Decoder, index2class
@@ -158,7 +161,8 @@ class OmniParser(nn.Module):
 
     # -- batched inference ------------------------------------------------------------------------
     @torch.no_grad()
-    def infer(self, img, mask, sequence, forced_instances=None, has_padding=None, lane=None, packed=None, ragged=False):
+    def infer(self, img, mask, sequence, forced_instances=None, has_padding=None, lane=None, packed=None, ragged=False,
+              windows=None, char_windows=None, clip_windows=False):
         """lane: a pipeline Lane (engine/pipeline.py) -- private decoder state + side streams, so several
         batches can be in flight on different HIP streams; None = the model's own state.
         packed = N (text spotting only): return (ids int32 [B, N, 34 + rec_length], probs [B, N, rec_length], n_inst [B]) device
@@ -168,7 +172,23 @@ class OmniParser(nn.Module):
         [3, h_b, w_b] device tensors (mask None), or a padded batch whose mask gives each image's extent (mask_extents).  Images
         of one size share an encoder pass; the decoders run once for all, each image's cross-attention reading its own M_b keys
         and no others (Decoder.project_memory key_len).  One size only: the padding-free path below, unchanged.  packed= is
-        padded-only."""
+        padded-only.
+        windows (text spotting only; None = the call above, bit for bit): a list of windows [x0, y0, x1, y1] in coordinate bins shared
+        by all images, or one such list per image (at most 64 each; utils/windows.py: grid_windows builds the reference's training
+        grids).  Every window is decoded under its own prompt (window_prompts) as a row of ONE point phase; the windows of an image
+        share its encoder pass, its K/V slabs and its cross-attention workgroups.  char_windows: a first-character window [c0, c1] for
+        all windows, one per window, or one list per image (args.use_char_window_prompt only).  The points are gathered on the
+        device (omp_window_points) and feed the polygon / recognition phases as in the plain call.  Per image the result is
+        ([pt (1,2N), poly (1,32N), rec (1,N,rec_length)], [probs (N,rec_length)], window (N,) int64): the reference's shape with the
+        instances of all windows concatenated in window order, and the index of the window each instance came from.
+        clip_windows=True keeps a point only if the reference's membership rule holds against its own window (x0 < x <= x1 and
+        y0 < y <= y1, dataset/collate_fn.py:80-81).  Off by default: the lower bounds are strict, so under the default window the
+        rule also drops bin 0, which the plain call returns.  Works with ragged=True; packed= and args.infer_vie are refused."""
+        windowed = windows is not None or char_windows is not None
+        if windowed and packed is not None:
+            raise ValueError('infer: windows= returns per-image results; packed= is the plain call\'s payload')
+        if windowed and self.args.infer_vie:
+            raise ValueError('infer: windows= is a text-spotting call; the KIE walk (args.infer_vie) reads one row per image')
         enc, dec = self.engine()
         side = None
         if lane is not None:
@@ -205,6 +225,11 @@ class OmniParser(nn.Module):
             prompt = [int(t) for t in sequence[0].reshape(-1).tolist()]
             poly_sos = int(sequence[1].reshape(-1)[0])
             rec_sos = int(sequence[2].reshape(-1)[0])
+            if windowed:   # [rows, n_prompt] prompt rows + rows per image instead of the one flat prompt
+                per_image = WN.resolve_windows(windows if windows is not None else [WN.default_window(a)], B)
+                cw = WN.resolve_char_windows(char_windows, per_image)
+                prompt = (torch.cat([WN.window_prompts(a, ws, c) for ws, c in zip(per_image, cw)], 0), [len(ws) for ws in per_image],
+                          bool(clip_windows))
             self._mark('kv_project')
             dstream = getattr(lane, 'dec_stream', None) if lane is not None else None
             if dstream is not None:
@@ -295,6 +320,8 @@ class OmniParser(nn.Module):
         a = self.args
         if packed is not None and a.infer_vie:   # before any work: the KIE branch below returns early
             raise ValueError('packed results are the text-spotting payload; KIE returns entity lists')
+        if isinstance(prompt, tuple):
+            return self._decode_windows(dec, kv, prompt, poly_sos, rec_sos, forced_instances, B, dev, side)
         pts = dec.decode_points(kv, prompt, forced_instances=forced_instances)
         self._mark('pt_decode')
         if a.infer_vie:
@@ -324,6 +351,38 @@ class OmniParser(nn.Module):
             sl = slice(r0, r0 + n)
             out.append(([points[sl].long().reshape(1, -1), poly[sl].reshape(1, -1), rec[sl].unsqueeze(0)],
                         [rprob[sl]]))
+            r0 += n
+        return out
+
+    def _decode_windows(self, dec, kv, prompt, poly_sos, rec_sos, forced_instances, B, dev, side):
+        """the windowed call: point phase of sum W_b rows -> omp_window_points (the points never visit the host; only the counts come
+        back, in one small copy, to size the next phases) -> polygon || recognition decoders over all windows' instances"""
+        a = self.args
+        prompts, rows_per_image, clip = prompt
+        st = dec.decode_points(kv, prompts, forced_instances=forced_instances, rows_per_image=rows_per_image)
+        ph, rows = st['ph'], st['rows']
+        points, _, cnt = ops.window_points(ph.seq, ph.finished, ph.lengths, st['row_image'], B, st['n_prompt'], st['sampled'], clip=clip)
+        row_count, _, row_start, image_count = ops.split_window_counts(cnt.cpu(), rows)
+        self._mark('pt_decode')
+        R = int(row_start[rows])
+        if R == 0:
+            return [None] * B
+        counts = image_count.tolist()
+        points = points[:R]
+        (poly, _), (rec, rprob) = dec.decode_poly_and_rec(kv, points, counts, poly_sos, rec_sos, a.rec_length,
+                                                          streams=(side or None) if side is not None else self._side_streams(dev))
+        poly, rec, rprob = poly.long(), rec.long(), rprob.clone()
+        self._mark('poly_rec_decode')
+        out, r0, w0 = [], 0, 0
+        for b in range(B):
+            n, W = counts[b], rows_per_image[b]
+            window = torch.repeat_interleave(torch.arange(W), row_count[w0:w0 + W].long())
+            w0 += W
+            if n == 0:
+                out.append(None)
+                continue
+            sl = slice(r0, r0 + n)
+            out.append(([points[sl].long().reshape(1, -1), poly[sl].reshape(1, -1), rec[sl].unsqueeze(0)], [rprob[sl]], window))
             r0 += n
         return out
 

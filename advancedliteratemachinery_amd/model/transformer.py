@@ -481,9 +481,16 @@ class Decoder(object):
         return S
 
     # -- greedy drivers ---------------------------------------------------------------------------
-    def decode_points(self, kv, prompt, max_new=None, forced_instances=None, poll=16):
+    def decode_points(self, kv, prompt, max_new=None, forced_instances=None, poll=16, rows_per_image=None):
         """Point decoder for B images in lock-step.  Returns per image (ids list, probs list) after
-        prompt strip and the reference's tail trim (transformer.py:131-141)."""
+        prompt strip and the reference's tail trim (transformer.py:131-141).
+        Window prompts: prompt as an int tensor [rows, n_prompt] with rows_per_image -- one count per image, each
+        in 1 .. 64, rows sorted by image -- decodes every row under its OWN prompt, the rows of an image sharing that image's memory;
+        the result then stays on the device (decode_point_rows).  A flat prompt list is the call above, unchanged."""
+        if torch.is_tensor(prompt) and prompt.dim() == 2:
+            return self.decode_point_rows(kv, prompt, rows_per_image, max_new=max_new, forced_instances=forced_instances, poll=poll)
+        if rows_per_image is not None:
+            raise ValueError('decode_points: rows_per_image goes with a [rows, n_prompt] prompt tensor')
         a, B = self.args, kv['B']
         n_prompt = len(prompt)
         limit = 1024 - n_prompt + 1  # beyond this the reference indexes past its position table
@@ -520,6 +527,57 @@ class Decoder(object):
                 ids = ids[:-1]
             out.append((ids, pr))
         return out
+
+    def decode_point_rows(self, kv, prompts, rows_per_image, max_new=None, forced_instances=None, poll=16):
+        """The point phase of a windowed call: R = sum(rows_per_image) rows, row r decoded under prompts[r], the W_b rows of image b
+        grouped into that image's cross-attention tiles (make_tiles(rows_per_image): one workgroup streams an (image, head) key range
+        once for up to 64 of its windows).  forced_instances and EOS apply per row (the sampling kernels keep finished / lengths per
+        row); the poll loop ends when every row has finished.
+        Which kernels a phase takes follows from its row count R = sum W_b and from max W_b, exactly as for the polygon / recognition
+        phases (phase_path reads it off the bound plan; DESIGN.md section 16 holds the table).
+        -> dict(ph, rows, n_prompt, sampled, row_image): the phase with its seq / probs / finished / lengths buffers ON THE DEVICE, as
+        omp_window_points reads them (ops.window_points); nothing but the poll flags has visited the host."""
+        a, B = self.args, kv['B']
+        counts = [int(n) for n in (rows_per_image if rows_per_image is not None else [])]
+        if len(counts) != B or min(counts) < 1 or max(counts) > 64:
+            raise ValueError('decode_point_rows: rows_per_image must hold B = %d counts in [1, 64], got %s' % (B, counts))
+        R = sum(counts)
+        if tuple(prompts.shape[:1]) != (R,) or prompts.dim() != 2:
+            raise ValueError('decode_point_rows: %d rows need a [%d, n_prompt] prompt tensor, got %s' % (R, R, tuple(prompts.shape)))
+        n_prompt = int(prompts.shape[1])
+        limit = 1024 - n_prompt + 1  # beyond this the reference indexes past its position table
+        S = min(a.pt_seq_length if max_new is None else max_new, limit)
+        suppress = forced_instances is not None
+        if suppress:
+            S = min((3 if a.infer_vie else 2) * forced_instances, limit)
+        tiles = self.make_tiles(counts)
+        ph = self._phase('pt', R, n_prompt - 1 + S, n_prompt + S + 1, self._n_split(tiles, kv['M']))
+        self._bind(ph, kv, tiles, n_prompt, suppress, a.infer_vie)
+        ph.seq.zero_(); ph.probs.zero_(); ph.finished.zero_(); ph.lengths.zero_(); ph.d_pos.zero_()
+        ph.seq[:, :n_prompt] = prompts.to(self.device, torch.int32)
+        total = n_prompt - 1 + S
+        done = 0
+        if suppress:
+            self._run(ph, 0, total)
+            done = total
+        else:
+            while done < total:
+                n = min(total - done, (n_prompt - 1 if done == 0 else 0) + poll)
+                self._run(ph, done, n)
+                done += n
+                if all(ph.finished.tolist()):   # the only host sync of the point phase
+                    break
+        row_image = torch.tensor([b for b, n in enumerate(counts) for _ in range(n)], dtype=torch.int32).to(self.device)
+        return dict(ph=ph, rows=R, n_prompt=n_prompt, sampled=done - (n_prompt - 1), row_image=row_image, rows_per_image=counts)
+
+    def phase_path(self, ph):
+        """What a bound phase runs, read off its plan (csrc/decoder.hip: step_launch): the Linear layers as 'chains' (row-owner chains,
+        plan.rows_fused), 'mid' (launch per Linear with the mid chain between self- and cross-attention), 'x3' (tiled split-bf16 GEMMs
+        of the parity engine) or 'few' (the few-row path: fused few-row kernels on the bf16 engine up to 63 rows, weight-streaming
+        kernels otherwise); and the cross-attention's q_tiles (rows of one image per workgroup / 16) and workgroup-level key splits."""
+        P = ph.plan
+        lin = 'chains' if P.rows_fused else ('mid' if P.layers[0].rows_mid else ('x3' if P.gemm_x3 else 'few'))
+        return dict(rows=int(P.R), linear=lin, q_tiles=int(P.q_tiles), n_split=int(P.n_split), tiles=int(P.n_tiles))
 
     def begin_instances(self, kind, kv, points, counts, sos, n_new, infer_vie=False):
         """Set up poly / rec decoding of R = sum(counts) instances (rows sorted by image).  points: int32

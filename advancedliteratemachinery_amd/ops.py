@@ -657,3 +657,34 @@ def lexicon_nearest(q_codes, q_len, q_lo, q_hi, pool, pool_bytes, offsets, L, be
                                         int(range_hint), ptr(best), stream())
     _lib.check(rc, 'omp_lexicon_nearest')
     return best
+
+
+def window_points(seq, finished, lengths, row_image, n_images, n_prompt, sampled, clip=False, cap=None):
+    """omp_window_points (csrc/window_points.hip; utils/windows.py: gather_points_cpu is the specification): the buffers of a finished
+    point phase -- seq int32 [rows, seq_ld], finished / lengths int32 [rows] -- and the row -> image table
+    -> (points int32 [cap, 2], inst_row int32 [cap], counts): counts is ONE int32 tensor [3 * rows + 1 + n_images] =
+    row_count | dropped | row_start (rows + 1 entries, the last one the total) | image_count, so that a caller fetches everything that
+    sizes the next phases in one copy (split_window_counts).  cap defaults to rows * (pairs a row can hold)."""
+    if seq.dim() != 2 or not (0 <= int(n_prompt) <= seq.shape[1]):
+        raise ValueError('seq must be [rows, seq_ld] with n_prompt inside a row')
+    rows, seq_ld = int(seq.shape[0]), int(seq.shape[1])
+    for name, t in (('seq', seq), ('finished', finished), ('lengths', lengths), ('row_image', row_image)):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.shape[0] != rows:
+            raise ValueError('%s must be a contiguous device int32 tensor with %d rows' % (name, rows))
+    if cap is None:
+        cap = rows * ((int(seq.shape[1]) - int(n_prompt)) // 2)
+    dev = seq.device
+    points = torch.empty(max(cap, 1), 2, dtype=torch.int32, device=dev)
+    inst_row = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(3 * rows + 1 + int(n_images), dtype=torch.int32, device=dev)
+    row_count, dropped, row_start, image_count = counts[:rows], counts[rows:2 * rows], counts[2 * rows:3 * rows + 1], counts[3 * rows + 1:]
+    rc = _lib.lib().omp_window_points(ptr(seq), seq_ld, ptr(finished), ptr(lengths), ptr(row_image), rows, int(n_images), int(n_prompt),
+                                      int(sampled), 1 if clip else 0, ptr(points), ptr(inst_row), int(cap),
+                                      ptr(row_count), ptr(dropped), ptr(row_start), ptr(image_count), stream())
+    _lib.check(rc, 'omp_window_points')
+    return points[:cap], inst_row[:cap], counts
+
+
+def split_window_counts(counts, rows):
+    """the counts tensor of window_points (on either side of the copy) -> (row_count, dropped, row_start, image_count)"""
+    return counts[:rows], counts[rows:2 * rows], counts[2 * rows:3 * rows + 1], counts[3 * rows + 1:]

@@ -616,6 +616,30 @@ int omp_lexicon_nearest(const uint8_t* q_codes, const int32_t* q_len, const int3
                         const uint8_t* pool, int64_t pool_bytes, const int32_t* offsets, int L, int range_hint,
                         uint64_t* best, omp_stream_t s);
 
+/* ---- window prompts: the points of a finished point phase, compacted on the device ----
+ * The point decoder's prompt holds a spatial window; an engine call may run several windows per image as rows of ONE point
+ * phase (the reference's forward takes any such prompt, model/transformer.py:102-141; its training draws them,
+ * dataset/collate_fn.py:46-115).  This entry point is the step between that phase and the polygon / recognition phases; it
+ * reads the phase's buffers as the sampling kernels left them (omp_decoder_plan.seq / finished / lengths):
+ *   seq        int32 [rows][seq_ld]: row r = its prompt (seq[r][0..3] = its window x0, y0, x1, y1), then the sampled tokens
+ *   finished, lengths  int32 [rows]: EOS flag and EOS position of every row (omp_head_softmax_mask_argmax)
+ *   row_image  int32 [rows]: the image of every row, in [0, n_images); rows outside that range count for no image
+ *   n_prompt, sampled  row r's tokens are seq[r][n_prompt .. end), end = lengths[r] if finished[r] else n_prompt + sampled, clamped
+ *              into [n_prompt, seq_ld]; an odd tail is dropped (transformer.py:138-139); the tokens are (x, y) pairs
+ *   clip       nonzero: keep a pair only if x0 < x <= x1 and y0 < y <= y1 against the row's own window (collate_fn.py:80-81,
+ *              verbatim: the lower bounds are strict, so the default window drops bin 0 too).  Needs n_prompt >= 4.
+ * Outputs, all int32 and all written by this call (the caller initialises nothing):
+ *   points [cap][2], inst_row [cap]: the kept pairs and their rows, in row order and inside a row in the decoder's order (a
+ *              stable compaction); entries at or beyond cap are not written (row_start[rows] still holds the full total)
+ *   row_count [rows], dropped [rows]: pairs kept / removed by the clip per row
+ *   row_start [rows + 1]: exclusive prefix sum of row_count; row_start[rows] = the total
+ *   image_count [n_images]: pairs kept per image (through row_image)
+ * utils/windows.py: gather_points_cpu is the specification; every output integer equals it.  Three launches (count, scan,
+ * copy); no allocation, no synchronisation. */
+int omp_window_points(const int32_t* seq, int seq_ld, const int32_t* finished, const int32_t* lengths, const int32_t* row_image,
+                      int rows, int n_images, int n_prompt, int sampled, int clip, int32_t* points, int32_t* inst_row, int cap,
+                      int32_t* row_count, int32_t* dropped, int32_t* row_start, int32_t* image_count, omp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
