@@ -351,7 +351,10 @@ def vit_patch_embed(img, w, bias, cls, pos, out_dtype):
 
 def vit_attn(q, K, Vt, out, B, T, nH, Mpad):
     """bf16 ViT self-attention on one layer's blocked slabs: q [B*T, nH*64], K [B, nH, Mpad, 64], Vt [B, nH, Mpad/32, 64, 32]
-    -> out [B*T, nH*64] (all heads, all images, one launch)."""
+    -> out [B*T, nH*64] (all heads, all images, one launch).
+    Slab contract: keys at and beyond T are padding.  Their K rows may hold anything (NaN included): the kernel masks their scores
+    before the softmax.  Their V^T slots must be ZERO, as the model's slabs are (allocated zeroed, the projections write keys < T
+    only): they are multiplied by a weight of exactly 0, and 0 * NaN would reach the output."""
     rc = _lib.lib().omp_vit_attn(ptr(q), q.stride(0), ptr(K), ptr(Vt), Mpad, ptr(out), out.stride(0), dt(q), B, T, nH, stream())
     _lib.check(rc, 'omp_vit_attn')
     return out
