@@ -116,7 +116,7 @@ def _n_images(images):
 
 @torch.no_grad()
 def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None,
-            windows=None, char_windows=None, clip_windows=False, grid=None):
+            windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou', suppress_order='first'):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
     Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
     ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
@@ -130,7 +130,16 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     for utils.windows.grid_windows(nx, ny, args.num_bins)), char_windows, clip_windows: window prompts (OmniParser.infer; DESIGN.md
     section 16) -- every window of an image is read under its own prompt in ONE engine call; an image's records are those of its
     windows in window order, and every record gains `window` (the index) and `window_bins` (its [x0, y0, x1, y1]).  Without these
-    arguments the records are the plain call's.  Text spotting only; composes with ragged= and lexicon=."""
+    arguments the records are the plain call's.  Text spotting only; composes with ragged= and lexicon=.
+    suppress (a float in (0, 1]), suppress_measure ('iou' | 'iomin'), suppress_order ('first' | 'score'): overlap suppression (DESIGN.md
+    section 17; utils/overlap.py) -- records of one image whose decoded polygons overlap by at least `suppress` are the same word: the
+    first in priority order ('first': record order, i.e. window order, then the decoder's; 'score': descending `score`, ties to the
+    lower index) stays and gains `merged`, the list of (window, index) of the records it absorbed (plain indices without windows; an
+    index counts the image's records before suppression), the others are removed.  The polygons are the raw ids on the device; all
+    images go through ONE device call, before lexicon= annotates the survivors.  Without suppress= the records are the plain call's."""
+    if suppress is not None:
+        from ..utils import overlap as OV
+        OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     if orig_sizes is None and targets is not None and args.infer_vie:
@@ -159,6 +168,9 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
         if per_image is not None:
             for rcd, w in zip(out[-1], r[2].tolist()):
                 rcd['window'], rcd['window_bins'] = int(w), list(per_image[b][w])
+    if suppress is not None:
+        out = OV.suppress_records(out, [None if r is None else r[0][1] for r in raw], args.num_bins, suppress, suppress_measure, suppress_order,
+                                  device=next(model.parameters()).device)
     if lexicon is not None:
         from ..utils import lexicon as LX
         matcher = LX.resolve_lexicon(lexicon, len(out), next(model.parameters()).device, args.chars)
@@ -168,7 +180,8 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
 
 @torch.no_grad()
 def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
-                   lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None):
+                   lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou',
+                   suppress_order='first'):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
@@ -176,10 +189,16 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     lexicon, lexicon_max_dist, lexicon_max_ratio: as predict (records gain `lex`, `lex_index`, `lex_dist`).
     windows, char_windows, clip_windows, grid: as predict (window prompts; records gain `window`, `window_bins`).  The bins of a
     window are fractions of the RESIZED image the model sees, which is the original image scaled: the same fractions of both.
+    suppress, suppress_measure, suppress_order: as predict (overlap suppression; survivors gain `merged`).
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+    skw = {}
+    if suppress is not None:
+        from ..utils import overlap as OV
+        OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
+        skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
     dev = next(model.parameters()).device
     if preprocessor is None:
         preprocessor = DevicePreprocessor(args.test_min_size, args.test_max_size, dev)
@@ -189,7 +208,7 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
                 'orig_size': (int(im.shape[0]), int(im.shape[1]))} for b, im in enumerate(imgs)]
     return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged, lexicon=lexicon,
                    lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio, windows=windows, char_windows=char_windows,
-                   clip_windows=clip_windows, grid=grid), preprocessor
+                   clip_windows=clip_windows, grid=grid, **skw), preprocessor
 
 
 def _meta(t):

@@ -54,7 +54,7 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 @torch.no_grad()
 def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
                        lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
-                       grid=None):
+                       grid=None, suppress=None, suppress_measure='iou', suppress_order='first'):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -69,11 +69,18 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     windows, char_windows, clip_windows, grid=(nx, ny): window prompts, as predict_images takes them: the
     spotter reads every window of every image in one engine call, the records gain `window` and `window_bins`, and the recogniser
     reads the crops of all windows' words exactly as it reads the plain call's.
+    suppress, suppress_measure, suppress_order: overlap suppression, as predict_images takes it: duplicates are
+    removed BEFORE the crops, so a duplicate is neither cropped nor recognised; survivors gain `merged`.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+    skw = {}
+    if suppress is not None:
+        from ..utils import overlap as OV
+        OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
+        skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
     if lexicon is not None:
@@ -82,7 +89,7 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
             lexicon = [list(w) if not isinstance(w, str) else w for w in lexicon]   # read a generator once, use it twice
     records, preprocessor = predict_images(omni_model, imgs, args, file_names=file_names, preprocessor=preprocessor, ragged=ragged,
                                            lexicon=lexicon, lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio,
-                                           windows=windows, char_windows=char_windows, clip_windows=clip_windows, grid=grid)
+                                           windows=windows, char_windows=char_windows, clip_windows=clip_windows, grid=grid, **skw)
     boxes, polys, owner = [], [], []
     for b, recs in enumerate(records):
         h, w = int(imgs[b].shape[0]), int(imgs[b].shape[1])

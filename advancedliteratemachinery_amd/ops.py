@@ -691,3 +691,60 @@ def window_points(seq, finished, lengths, row_image, n_images, n_prompt, sampled
 def split_window_counts(counts, rows):
     """the counts tensor of window_points (on either side of the copy) -> (row_count, dropped, row_start, image_count)"""
     return counts[:rows], counts[rows:2 * rows], counts[2 * rows:3 * rows + 1], counts[3 * rows + 1:]
+
+
+def polygon_overlap(polys, group_start, order, mask_start, mask_words, grid, t, measure, inter_start=None, inter_total=0, out=None):
+    """omp_polygon_overlap (csrc/overlap.hip; utils/overlap.py holds the specification and packs the tables): polys int32 [N, 32],
+    group_start int32 [G + 1], order int32 [N], mask_start int64 [G + 1] (utils.overlap.mask_layout; mask_words = its last entry),
+    measure 0 = IoU / 1 = intersection over the smaller area, t in permille; inter_start int64 [G + 1] with inter_total asks for the
+    dense intersection matrices too.
+    -> dict(ints: ONE int32 tensor [6 N + G] = bbox [N, 4] | area [N] | owner [N] | kept [G] (the last two are polygon_keep's, so that a
+    caller fetches everything in one copy: split_overlap_ints), bbox, area: views of it, mask: int64 [mask_words] holding the uint64
+    words, inter: int32 [inter_total] or None)."""
+    N, G = int(polys.shape[0]), int(group_start.numel()) - 1
+    for name, tt, dtype, numel in (('polys', polys, torch.int32, 32 * N), ('group_start', group_start, torch.int32, G + 1), ('order', order, torch.int32, N),
+                                   ('mask_start', mask_start, torch.int64, G + 1), ('inter_start', inter_start, torch.int64, G + 1)):
+        if tt is None:
+            continue
+        if not tt.is_cuda or tt.dtype != dtype or not tt.is_contiguous() or tt.numel() != numel:
+            raise ValueError('%s must be a contiguous device %s tensor with %d elements' % (name, dtype, numel))
+    if polys.dim() != 2 or polys.shape[1] != 32 or N < 1 or G < 1 or int(mask_words) < 1:
+        raise ValueError('polys must be [N, 32] with at least one polygon and one group')
+    dev = polys.device
+    if out is None:
+        out = torch.empty(6 * N + G, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != 6 * N + G or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor with %d elements' % (6 * N + G))
+    bbox, area = out[:4 * N], out[4 * N:5 * N]
+    mask = torch.empty(int(mask_words), dtype=torch.int64, device=dev)
+    inter = torch.empty(int(inter_total), dtype=torch.int32, device=dev) if inter_start is not None else None
+    rc = _lib.lib().omp_polygon_overlap(ptr(polys), N, ptr(group_start), G, ptr(order), ptr(mask_start), int(mask_words), int(grid), int(t),
+                                        int(measure), ptr(area), ptr(bbox), ptr(mask), ptr(inter), ptr(inter_start),
+                                        int(inter_total) if inter is not None else 0, stream())
+    _lib.check(rc, 'omp_polygon_overlap')
+    return dict(ints=out, bbox=bbox.view(N, 4), area=area, mask=mask, inter=inter)
+
+
+def polygon_keep(mask, mask_start, group_start, order, n, out=None):
+    """omp_polygon_keep: the greedy pass over polygon_overlap's mask, in the priority order the mask was built for.
+    -> the int32 tensor [6 n + G] of polygon_overlap (`out`, or a new one whose first 5 n entries are not written) with owner at
+    [5 n, 6 n) and kept at [6 n, 6 n + G): split_overlap_ints."""
+    G = int(group_start.numel()) - 1
+    for name, tt, dtype, numel in (('mask', mask, torch.int64, int(mask.numel())), ('mask_start', mask_start, torch.int64, G + 1),
+                                   ('group_start', group_start, torch.int32, G + 1), ('order', order, torch.int32, int(n))):
+        if not tt.is_cuda or tt.dtype != dtype or not tt.is_contiguous() or tt.numel() != numel:
+            raise ValueError('%s must be a contiguous device %s tensor with %d elements' % (name, dtype, numel))
+    n = int(n)
+    if out is None:
+        out = torch.empty(6 * n + G, dtype=torch.int32, device=mask.device)
+    elif out.dtype != torch.int32 or out.numel() != 6 * n + G or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor with %d elements' % (6 * n + G))
+    rc = _lib.lib().omp_polygon_keep(ptr(mask), ptr(mask_start), int(mask.numel()), ptr(group_start), G, n, ptr(order), ptr(out[5 * n:6 * n]),
+                                     ptr(out[6 * n:]), stream())
+    _lib.check(rc, 'omp_polygon_keep')
+    return out
+
+
+def split_overlap_ints(ints, n):
+    """the int32 tensor of polygon_overlap / polygon_keep (on either side of the copy) -> (bbox [n, 4], area, owner, kept)"""
+    return ints[:4 * n].reshape(n, 4), ints[4 * n:5 * n], ints[5 * n:6 * n], ints[6 * n:]

@@ -640,6 +640,41 @@ int omp_window_points(const int32_t* seq, int seq_ld, const int32_t* finished, c
                       int rows, int n_images, int n_prompt, int sampled, int clip, int32_t* points, int32_t* inst_row, int cap,
                       int32_t* row_count, int32_t* dropped, int32_t* row_start, int32_t* image_count, omp_stream_t s);
 
+/* ---- overlap suppression: which decoded polygons are the same word -------------
+ * Neither reference project removes duplicate detections (shapely is in OmniParser's requirements and nothing imports it); windows
+ * that overlap, the whole-page window next to a grid, or the autoregressive point decoder itself return a word more than once.
+ * utils/overlap.py holds the specification (coverage_cpu, pair_overlap_cpu, suppress_cpu); every output integer equals it.
+ *   polys       int32 [n][32]: 16 points (x0, y0, ..., x15, y15) in coordinate bins, the polygon decoder's tokens; every coordinate is
+ *               CLAMPED on the device to [0, grid - 1]; 2 <= grid <= 4096
+ *   coverage    a polygon covers the bin centres (i + 0.5, j + 0.5), 0 <= i, j < grid - 1, inside it under the even-odd rule, decided in
+ *               doubled integer coordinates (vertices even, samples odd): edge (x1, y1) -> (x2, y2), oriented so that q = y2 - y1 > 0,
+ *               counts for sample (xs, ys) when (y1 < ys) != (y2 < ys) and xs q < x1 q + (ys - y1) (x2 - x1)
+ *   group_start int32 [n_groups + 1]: polygons group_start[g] .. group_start[g + 1] - 1 form group g (an image); only polygons of one
+ *               group interact; entries are clamped into [0, n] on the device.  A group holds at most 8192 polygons.
+ *   order       int32 [n]: the priority order, grouped like the polygons: order[group_start[g] + p] is the polygon at priority position p
+ *               of group g (a global index, clamped into the group on the device)
+ *   t, measure  permille threshold 1 .. 1000 and 0 = IoU / 1 = intersection over the smaller area: b overlaps a when inter > 0 and
+ *               1000 inter >= t (area_a + area_b - inter), resp. >= t min(area_a, area_b); 64-bit products
+ *   mask_start  int64 [n_groups + 1]: group g's bitmask begins at word mask_start[g] and holds n_g rows of W_g = ceil(n_g / 64) words;
+ *               mask_start[n_groups] = mask_words (at most 2^32)
+ * Outputs, all written by the call (the caller initialises nothing):
+ *   area  int32 [n]: samples inside each polygon;  bbox int32 [n][4]: x0, y0, x1, y1 of the clamped points
+ *   mask  uint64 [mask_words]: row p, bit q (word q / 64, bit q % 64) is set when q > p and the polygons at priority positions p and
+ *         q overlap; every other bit is 0
+ *   inter int32 [inter_total] or NULL: group g's dense n_g x n_g matrix at inter_start[g] (int64 [n_groups + 1]), in POLYGON order,
+ *         inter[a][b] = samples inside both, the diagonal = area.  With NULL the area-ratio prefilter also applies.
+ * Two launches (a wave per polygon; a wave per mask word); no allocation, no synchronisation. */
+int omp_polygon_overlap(const int32_t* polys, int n, const int32_t* group_start, int n_groups, const int32_t* order,
+                        const int64_t* mask_start, int64_t mask_words, int grid, int t, int measure, int32_t* area, int32_t* bbox,
+                        uint64_t* mask, int32_t* inter, const int64_t* inter_start, int64_t inter_total, omp_stream_t s);
+/* Greedy suppression over omp_polygon_overlap's mask: walk each group's positions in priority order; a polygon is kept unless an
+ * earlier kept polygon overlaps it.  owner int32 [n]: the polygon itself when kept, else the first kept polygon, in priority order,
+ * that overlaps it.  kept int32 [n_groups]: polygons kept per group; -1 for a group that is REFUSED on the device (more than 8192
+ * polygons, or a mask range outside [0, mask_words)), whose owner entries are the polygons themselves.  One launch, one workgroup
+ * per group. */
+int omp_polygon_keep(const uint64_t* mask, const int64_t* mask_start, int64_t mask_words, const int32_t* group_start, int n_groups, int n,
+                     const int32_t* order, int32_t* owner, int32_t* kept, omp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
