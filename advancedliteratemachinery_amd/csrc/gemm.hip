@@ -468,12 +468,14 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
   }
   if (n >= p.N) return;
   if (vec_path) {
+    const bool bias_rows = bias != nullptr && p.bias_m;
     auto store_rows = [&](auto ACT) {
 #pragma unroll
       for (int pass = 0; pass < BM / RPP; ++pass) {
         const int r = pass * RPP + rsub;
         const int64_t m = m0 + r;
         if (m < p.M) {
+          const float bm = bias_rows ? bias[m] : 0.f;   // bias_along_m: the row's bias, as the 4-value path below adds it
           float v[CH];
 #pragma unroll
           for (int q = 0; q < CH; q += 4) {
@@ -483,6 +485,7 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
 #pragma unroll
           for (int q = 0; q < CH; ++q) {
             v[q] += bcol[q];
+            if (bias_rows) v[q] += bm;   // a branch, not + 0: a product without bias_along_m keeps its bits (-0 + 0 = +0)
             if constexpr (decltype(ACT)::value == OMP_ACT_GELU && !std::is_same<TOut, bf16_t>::value) v[q] = gelu_erf(v[q]);
             if constexpr (decltype(ACT)::value == OMP_ACT_RELU) v[q] = fmaxf(v[q], 0.0f);
           }
@@ -753,6 +756,10 @@ int launch_small_t(const GemmP& p, hipStream_t st) {
   const size_t ab = LN ? (size_t)MF * 16 * (p.K * sizeof(T) + 16) : 0;
   const size_t smem = red + ab;
   constexpr auto kern = gemm_small<T, TOut, MF, LN>;
+  if (smem > 160 * 1024) {   // the normalised rows of the LayerNorm prologue do not fit (fp32 operands, more than 32 rows, K > 544)
+    omp_set_error("omp_gemm_bias_act: the fused LayerNorm of %lld fp32 rows of K=%d needs %zu bytes of LDS (160 KB at most): at most 32 rows, or K <= 544", (long long)p.M, p.K, smem);
+    return OMP_ERR_INVALID;
+  }
   if (smem > 48 * 1024) {
     if (const int rc = omp_raise_lds<kern>("omp_gemm_bias_act")) return rc;
   }

@@ -426,6 +426,31 @@ def kept(buf, rows, bits):
     return bool((buf[rows:].view(_ibits(buf.dtype)) == bits).all().item())
 
 
+VIEW_LEAD, VIEW_OFF = 8, 8           # guard rows before / after and guard columns before a guarded_view (multiples of 8: 16-byte bases)
+
+
+def guarded_view(rows, width, pitch, dtype, bits, fill=None, device=DEV, tail=VIEW_LEAD):
+    """guarded() with a row pitch and guards on every side: a [VIEW_LEAD + rows + tail, pitch] buffer of `bits` and its view
+    [rows, width] at row VIEW_LEAD, column VIEW_OFF (pitch >= VIEW_OFF + width), = fill where given -> (buffer, view).  The view's
+    base stays 16-byte aligned whatever the pitch."""
+    assert pitch >= VIEW_OFF + width
+    buf = torch.empty((VIEW_LEAD + rows + tail, pitch), dtype=dtype, device=device)
+    buf.view(_ibits(dtype)).fill_(bits)
+    view = buf[VIEW_LEAD:VIEW_LEAD + rows, VIEW_OFF:VIEW_OFF + width]
+    if fill is not None:
+        view.copy_(fill)
+    return buf, view
+
+
+def kept_view(buf, rows, width, bits):
+    """(guard rows before and after the view of guarded_view still hold bits, so do the gap columns beside its rows)"""
+    b = buf.view(_ibits(buf.dtype))
+    mid = b[VIEW_LEAD:VIEW_LEAD + rows]
+    rows_ok = bool((b[:VIEW_LEAD] == bits).all().item()) and bool((b[VIEW_LEAD + rows:] == bits).all().item())
+    cols_ok = bool((mid[:, :VIEW_OFF] == bits).all().item()) and bool((mid[:, VIEW_OFF + width:] == bits).all().item())
+    return rows_ok, cols_ok
+
+
 def nan_bits(dt):
     return F32_NAN if dt == torch.float32 else BF16_NAN
 
