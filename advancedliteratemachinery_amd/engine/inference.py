@@ -116,7 +116,8 @@ def _n_images(images):
 
 @torch.no_grad()
 def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None,
-            windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou', suppress_order='first'):
+            windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou', suppress_order='first',
+            reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
     Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
     ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
@@ -136,7 +137,17 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     first in priority order ('first': record order, i.e. window order, then the decoder's; 'score': descending `score`, ties to the
     lower index) stays and gains `merged`, the list of (window, index) of the records it absorbed (plain indices without windows; an
     index counts the image's records before suppression), the others are removed.  The polygons are the raw ids on the device; all
-    images go through ONE device call, before lexicon= annotates the survivors.  Without suppress= the records are the plain call's."""
+    images go through ONE device call, before lexicon= annotates the survivors.  Without suppress= the records are the plain call's.
+    reading_order=True, line_gap, line_back, line_offset (floats in [0, 10], in units of a word's height): reading order (DESIGN.md
+    section 18; utils/reading.py) -- the words of an image are linked into text lines (a word follows another when it starts within
+    line_gap heights after its end, at most line_back heights before it, and at most line_offset heights off its axis, in both words'
+    frames), the lines are ordered top to bottom, every record gains `line` and `line_pos`, and each image's list is reordered
+    accordingly (utils.reading.page_lines joins it into strings).  It runs on the raw polygon ids on the device, ONE device call for
+    all images, after suppress= (on the survivors) and before lexicon=; `merged` indices keep counting the records before suppression.
+    Without reading_order the records are the plain call's."""
+    if reading_order:
+        from ..utils import reading as RD
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
     if suppress is not None:
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
@@ -156,21 +167,27 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged, **wkw)
     if args.infer_vie:
         return [r if r is not None else [] for r in raw]
-    out = []
+    out, sizes = [], []
     for b, r in enumerate(raw):
+        tgt = (targets[b] if targets is not None else
+               {'file_name': str(b), 'orig_size': nt[b] if ragged else (nt.tensors.shape[2], nt.tensors.shape[3])})
+        sizes.append(tgt['orig_size'])
         if r is None:
             out.append([])
             continue
-        tgt = (targets[b] if targets is not None else
-               {'file_name': str(b), 'orig_size': nt[b] if ragged else (nt.tensors.shape[2], nt.tensors.shape[3])})
         seq_cpu = [t[0].cpu() for t in r[0]]
         out.append(decode_pred_seq(seq_cpu, r[1][0].cpu(), tgt, args))
         if per_image is not None:
             for rcd, w in zip(out[-1], r[2].tolist()):
                 rcd['window'], rcd['window_bins'] = int(w), list(per_image[b][w])
+    rows = None
     if suppress is not None:
+        rows = []
         out = OV.suppress_records(out, [None if r is None else r[0][1] for r in raw], args.num_bins, suppress, suppress_measure, suppress_order,
-                                  device=next(model.parameters()).device)
+                                  device=next(model.parameters()).device, kept_rows=rows)
+    if reading_order:
+        out = RD.order_records(out, [None if r is None else r[0][1] for r in raw], sizes, args.num_bins, line_gap, line_back, line_offset, rows=rows,
+                               device=next(model.parameters()).device)
     if lexicon is not None:
         from ..utils import lexicon as LX
         matcher = LX.resolve_lexicon(lexicon, len(out), next(model.parameters()).device, args.chars)
@@ -181,7 +198,7 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
 @torch.no_grad()
 def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
                    lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou',
-                   suppress_order='first'):
+                   suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
@@ -190,6 +207,8 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     windows, char_windows, clip_windows, grid: as predict (window prompts; records gain `window`, `window_bins`).  The bins of a
     window are fractions of the RESIZED image the model sees, which is the original image scaled: the same fractions of both.
     suppress, suppress_measure, suppress_order: as predict (overlap suppression; survivors gain `merged`).
+    reading_order, line_gap, line_back, line_offset: as predict (records gain `line`, `line_pos` and come in reading order); the
+    aspect of every image is that of the ORIGINAL image, whose size scales the polygons.
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
     if lexicon is not None and args.infer_vie:
@@ -199,6 +218,10 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
         skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
+    if reading_order:
+        from ..utils import reading as RD
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
+        skw.update(reading_order=True, line_gap=line_gap, line_back=line_back, line_offset=line_offset)
     dev = next(model.parameters()).device
     if preprocessor is None:
         preprocessor = DevicePreprocessor(args.test_min_size, args.test_max_size, dev)

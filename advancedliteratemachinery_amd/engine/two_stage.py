@@ -54,7 +54,8 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 @torch.no_grad()
 def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
                        lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
-                       grid=None, suppress=None, suppress_measure='iou', suppress_order='first'):
+                       grid=None, suppress=None, suppress_measure='iou', suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5,
+                       line_offset=0.5):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -71,6 +72,9 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     reads the crops of all windows' words exactly as it reads the plain call's.
     suppress, suppress_measure, suppress_order: overlap suppression, as predict_images takes it: duplicates are
     removed BEFORE the crops, so a duplicate is neither cropped nor recognised; survivors gain `merged`.
+    reading_order, line_gap, line_back, line_offset: reading order, as predict_images takes it: the records are
+    put into text lines and reading order BEFORE the crops, so the crops are read in that order and `mgp_*` land on the reordered
+    records; utils.reading.page_lines(records, field='mgp_text') joins an image's lines.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
@@ -81,6 +85,10 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
         skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
+    if reading_order:
+        from ..utils import reading as RD
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
+        skw.update(reading_order=True, line_gap=line_gap, line_back=line_back, line_offset=line_offset)
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
     if lexicon is not None:

@@ -5,6 +5,7 @@ libomp355.so.  All wrappers launch on torch's CURRENT stream and never synchroni
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -748,3 +749,51 @@ def polygon_keep(mask, mask_start, group_start, order, n, out=None):
 def split_overlap_ints(ints, n):
     """the int32 tensor of polygon_overlap / polygon_keep (on either side of the copy) -> (bbox [n, 4], area, owner, kept)"""
     return ints[:4 * n].reshape(n, 4), ints[4 * n:5 * n], ints[5 * n:6 * n], ints[6 * n:]
+
+
+def _reading_tables(polys, tables, host_tables, n_groups):
+    N, G = int(polys.shape[0]), int(n_groups)
+    for name, tt, numel in (('polys', polys, 32 * N), ('tables', tables, 3 * G + 1)):
+        if not tt.is_cuda or tt.dtype != torch.int32 or not tt.is_contiguous() or tt.numel() != numel:
+            raise ValueError('%s must be a contiguous device int32 tensor with %d elements' % (name, numel))
+    if polys.dim() != 2 or polys.shape[1] != 32:
+        raise ValueError('polys must be [N, 32]')
+    host = np.ascontiguousarray(host_tables, dtype=np.int32).reshape(-1)
+    if host.size != 3 * G + 1:
+        raise ValueError('host_tables must hold %d int32 (group_start [G + 1], aspect [G, 2]), got %d' % (3 * G + 1, host.size))
+    return N, G, host
+
+
+def reading_links(polys, tables, host_tables, n_groups, grid, gap, back, offset):
+    """omp_reading_links (csrc/reading.hip; utils/reading.py holds the specification): polys int32 [N, 32]; tables device int32
+    [3 G + 1] = group_start [G + 1] | aspect [G, 2]; host_tables the same numbers on the host, which the entry point checks before
+    it launches; gap, back, offset in permille.  -> (succ0 int32 [N], cost0 int64 [N]): every word's best follower before resolution."""
+    N, G, host = _reading_tables(polys, tables, host_tables, n_groups)
+    succ0 = torch.empty(N, dtype=torch.int32, device=polys.device)
+    cost0 = torch.empty(N, dtype=torch.int64, device=polys.device)
+    rc = _lib.lib().omp_reading_links(ptr(polys), N, ptr(tables), host.ctypes.data, G, int(grid), int(gap), int(back), int(offset), ptr(succ0),
+                                      ptr(cost0), stream())
+    _lib.check(rc, 'omp_reading_links')
+    return succ0, cost0
+
+
+def reading_lines(polys, tables, host_tables, n_groups, grid, succ0, cost0, out=None):
+    """omp_reading_lines: reading_links' candidates -> lines.  -> ONE int32 tensor [5 N + G] = succ | pred | line | line_pos | rank |
+    n_lines (split_reading_ints), so that a caller fetches everything in one copy."""
+    N, G, host = _reading_tables(polys, tables, host_tables, n_groups)
+    for name, tt, dtype in (('succ0', succ0, torch.int32), ('cost0', cost0, torch.int64)):
+        if not tt.is_cuda or tt.dtype != dtype or not tt.is_contiguous() or tt.numel() != N:
+            raise ValueError('%s must be a contiguous device %s tensor with %d elements' % (name, dtype, N))
+    if out is None:
+        out = torch.empty(5 * N + G, dtype=torch.int32, device=polys.device)
+    elif out.dtype != torch.int32 or out.numel() != 5 * N + G or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor with %d elements' % (5 * N + G))
+    rc = _lib.lib().omp_reading_lines(ptr(polys), N, ptr(tables), host.ctypes.data, G, int(grid), ptr(succ0), ptr(cost0), ptr(out[:N]), ptr(out[N:2 * N]),
+                                      ptr(out[2 * N:3 * N]), ptr(out[3 * N:4 * N]), ptr(out[4 * N:5 * N]), ptr(out[5 * N:]), stream())
+    _lib.check(rc, 'omp_reading_lines')
+    return out
+
+
+def split_reading_ints(ints, n):
+    """the int32 tensor of reading_lines (on either side of the copy) -> (succ, pred, line, line_pos, rank, n_lines)"""
+    return tuple(ints[k * n:(k + 1) * n] for k in range(5)) + (ints[5 * n:],)

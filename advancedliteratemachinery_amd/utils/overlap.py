@@ -321,18 +321,21 @@ def check_suppress_args(suppress, measure, order, infer_vie=False):
     return permille(suppress)
 
 
-def suppress_records(records, raw_polys, grid, suppress, measure='iou', order='first', suppressor=None, device=None):
+def suppress_records(records, raw_polys, grid, suppress, measure='iou', order='first', suppressor=None, device=None, kept_rows=None):
     """records: per image the list of record dicts, in the engine's order.  raw_polys: per image the polygon decoder's ids for those
     records ([n_b, 32] tensors, None or empty for an image without records), on the device.  One device call for all images
     (`suppressor`: an OverlapSuppressor, or anything with its __call__; default: one on `device`).  -> the filtered lists: suppressed
     records are removed, every survivor gains `merged`, the (window, index) of the records it absorbed -- plain indices without
-    windows; index counts the image's records before suppression."""
+    windows; index counts the image's records before suppression.  kept_rows: a list that receives, per image, the rows of raw_polys
+    (indices before suppression) of the survivors, in the order of the returned records."""
     import torch
     t = check_suppress_args(suppress, measure, order)
     counts = [len(r) for r in records]
     gs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     N = int(gs[-1])
     if N == 0:
+        if kept_rows is not None:
+            kept_rows.extend([] for _ in records)
         return [list(r) for r in records]
     parts = []
     for b, (n, rp) in enumerate(zip(counts, raw_polys)):
@@ -352,11 +355,14 @@ def suppress_records(records, raw_polys, grid, suppress, measure='iou', order='f
     out = []
     for b, recs in enumerate(records):
         lo = int(gs[b])
-        kept = []
+        kept, rows = [], []
         for i, r in enumerate(recs):
             if int(owner[lo + i]) == lo + i:
                 r['merged'] = []
                 kept.append(r)
+                rows.append(i)
+        if kept_rows is not None:
+            kept_rows.append(rows)
         for i, r in enumerate(recs):
             o = int(owner[lo + i]) - lo
             if o != i:

@@ -675,6 +675,35 @@ int omp_polygon_overlap(const int32_t* polys, int n, const int32_t* group_start,
 int omp_polygon_keep(const uint64_t* mask, const int64_t* mask_start, int64_t mask_words, const int32_t* group_start, int n_groups, int n,
                      const int32_t* order, int32_t* owner, int32_t* kept, omp_stream_t s);
 
+/* ---- reading order: words -> text lines -> the order a reader takes them in ----
+ * Neither reference project orders its words: they leave the engine in decoder order.  utils/reading.py holds the specification
+ * (features_cpu, links_cpu, lines_cpu); every output integer equals it.  Integers only.
+ *   polys       int32 [n][32], 16-byte aligned: 16 points in coordinate bins, CLAMPED on the device to [0, grid - 1]; 2 <= grid <= 4096
+ *   tables      device int32 [3 n_groups + 1]: group_start [n_groups + 1] (words group_start[g] .. group_start[g + 1] - 1 are image g's;
+ *               only words of one group interact), then aspect [n_groups][2] = (ax, ay), 1 .. 256: geometry is done on (x ax, y ay)
+ *   host_tables the same int32 [3 n_groups + 1] in HOST memory: checked before anything is launched (group_start rises from 0 to n,
+ *               every aspect in 1 .. 256); the device clamps what it reads all the same
+ *   gap, back, offset  permille, 0 .. 10000
+ *   features    T[k] = P[k], B[k] = P[15 - k]; L = T[0] + B[0], R = T[7] + B[7], d = R - L ((1, 0) when 0), H = sum_k |(T[k] - B[k]) x d|
+ *   link a -> b with v = L_b - R_a: d_a . d_b > 0, -back H_a <= 4000 v . d_a <= gap H_a, 4000 |v x d_a| <= offset H_a,
+ *               4000 |v x d_b| <= offset H_b; cost = |v|^2 (below 2^46)
+ * omp_reading_links: succ0 int32 [n] = the passing b of least cost (ties to the lower b; a global index) or -1, cost0 int64 [n] = its
+ * cost or -1.  One launch: workgroups of 256 words inside one group, candidates staged through LDS in tiles of 256.
+ * n == 0 returns OMP_OK without a launch. */
+int omp_reading_links(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid, int gap, int back,
+                      int offset, int32_t* succ0, int64_t* cost0, omp_stream_t s);
+/* Lines from omp_reading_links' candidates, one workgroup per group, everything in LDS: a word claimed by several keeps the
+ * predecessor of least (cost, a) and the losers end their lines; a cycle is cut in front of its lowest member; lines are ordered by
+ * the mean of their members' sum_k y_k ay (compared exactly), then the head's L_x, then the head's index.
+ *   succ, pred  int32 [n]: global indices, -1 at a line's ends;  line, line_pos, rank int32 [n]: the line's number in its group, the
+ *               distance from the line's head, the position in the group with the lines concatenated
+ *   n_lines     int32 [n_groups]: lines per group; -1 for a group that is REFUSED on the device (more than 8192 words), of whose
+ *               words nothing is written
+ * One launch.  n == 0 returns OMP_OK without a launch. */
+int omp_reading_lines(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid,
+                      const int32_t* succ0, const int64_t* cost0, int32_t* succ, int32_t* pred, int32_t* line, int32_t* line_pos,
+                      int32_t* rank, int32_t* n_lines, omp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
