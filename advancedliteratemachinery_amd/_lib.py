@@ -147,6 +147,7 @@ _SIGS = {
     'omp_polygon_keep': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int] + [c_void_p] * 4),
     'omp_reading_links': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3),
     'omp_reading_lines': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 9),
+    'omp_reading_blocks': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 9),
     'omp_ctx_create': (c_int, [ctypes.POINTER(c_void_p)]),
     'omp_ctx_destroy': (c_int, [c_void_p]),
     'omp_ctx_make_current': (c_int, [c_void_p]),

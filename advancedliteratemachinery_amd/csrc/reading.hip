@@ -333,6 +333,250 @@ int reading_check(const char* who, const int32_t* polys, int n, const int32_t* t
   return OMP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// blocks: a recursive XY-cut over the lines (utils/reading.py: blocks_cpu is the specification)
+// ---------------------------------------------------------------------------------------------
+//   reading_blocks_kernel  a workgroup of 1024 threads per group, dynamic LDS of 16 bytes per slot + 64, slots = the call's largest group
+//                          rounded up to a power of two (the sort's size), at least 8.  Thread t owns words / atoms / sorted positions
+//                          t, t + 1024, ... (at most 8) everywhere but in the scans, where it owns the 8 consecutive positions 8 t ...
+//     1 per axis (y, then x): every word's inflated interval, biased by 2^38 into an unsigned below 2^39; per-line min / max by 64-bit
+//       LDS atomics (region A = lo, region B = hi, 8 bytes per slot each)
+//     2 region A becomes the keys lo << 13 | line and is sorted (bitonic, 64-bit) ONCE per axis: the position is the atom's rank r under
+//       (lo, line number).  hr = the number of atoms whose lo is <= the atom's hi (a binary search in the sorted keys): lo_b > hi_a is
+//       exactly r_b >= hr_a, and hr rises with hi, so the levels never see an interval again.  Kept in registers across the axes:
+//       r of the own atoms, (hr << 13 | atom) of the own ranks.
+//     3 regions for the levels, 4 bytes per slot each: keys | TY | TX | seg (T?[rank] = hr << 13 | atom).  Per level: keys =
+//       seg << 13 | r (26 bits; pads 0xffffffff), bitonic sort (32-bit), then over the sorted order a max-scan of seg << 14 | hr -- segments
+//       rise along the order, so the plain maximum IS the segmented one -- the flags (first of its segment, or r >= the maximum before
+//       it), their sum-scan = the new segment ids, and the total, which every thread reads: the stopping rule is block-uniform.
+//     4 keys = seg << 13 | old line, sorted: the position is the new line number
+//     5 line lengths (LDS atomicAdd) in the new order, exclusive scan -> the first rank of every line; per-word outputs
+// Every index is clamped or tested: a word's line into [0, atoms - 1], the atoms of a group into [1, words].
+constexpr int RB_MIN_SLOTS = 8;
+constexpr int RB_MAX_DEPTH = 16;
+constexpr int RB_EXTRA = 64;                            // bytes behind the slots: 16 wave partials
+constexpr long long RB_BIAS = 1ll << 38;
+
+#define RB_FOR_OWN(k, i, count)                         \
+  _Pragma("unroll") for (int k = 0; k < RD_OWN; ++k)    \
+    if (const int i = tid + k * RD_THREADS; i < (count))
+
+// a[0 .. n2 - 1] ascending, n2 a power of two; a barrier behind every step, the caller has one in front
+template <typename T>
+__device__ __forceinline__ void rb_sort(T* a, int n2, int tid) {
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (n2 >> 1); t += RD_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+        const T x = a[i], y = a[p];
+        if ((x > y) == ((i & k) == 0)) {
+          a[i] = y;
+          a[p] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// scan of one NON-NEGATIVE value per thread over the workgroup, maximum or sum (identity 0): returns the inclusive value, *excl = over
+// the threads in front, *total = over all.  Two barriers; every thread of the workgroup calls it.
+template <bool MAX>
+__device__ __forceinline__ int rb_scan(int v, int* part, int tid, int* excl, int* total) {
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(v, d, 64);
+    if (lane >= d) v = MAX ? max(v, o) : v + o;
+  }
+  int ex = __shfl_up(v, 1, 64);
+  if (lane == 0) ex = 0;
+  if (lane == 63) part[wave] = v;
+  __syncthreads();
+  int base = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < RD_THREADS / 64; ++w) {
+    const int pw = part[w];
+    if (w < wave) base = MAX ? max(base, pw) : base + pw;
+    all = MAX ? max(all, pw) : all + pw;
+  }
+  __syncthreads();   // part may be written again
+  *total = all;
+  *excl = MAX ? max(base, ex) : base + ex;
+  return MAX ? max(base, v) : base + v;
+}
+
+__global__ __launch_bounds__(RD_THREADS) void reading_blocks_kernel(const int32_t* __restrict__ polys, int n, const int32_t* __restrict__ tables, int n_groups,
+                                                                   int slots, int grid, int gap_x, int gap_y, int depth, const int32_t* __restrict__ line_in,
+                                                                   const int32_t* __restrict__ pos_in, const int32_t* __restrict__ n_lines_in,
+                                                                   int32_t* __restrict__ block, int32_t* __restrict__ line, int32_t* __restrict__ rank,
+                                                                   int32_t* __restrict__ n_blocks, int32_t* __restrict__ levels) {
+  extern __shared__ __align__(16) unsigned char rb_lds[];   // 16 slots + RB_EXTRA bytes; no static LDS beside it (omp_raise_lds)
+  const int tid = threadIdx.x, g = blockIdx.x;
+  const Group G = load_group(tables, n_groups, g, n);
+  const int g0 = G.g0, ng = G.g1 - G.g0;
+  if (ng > RD_MAX_GROUP || ng > slots) {   // refused: nothing else is written
+    if (tid == 0) n_blocks[g] = -1;
+    return;
+  }
+  if (ng == 0) {
+    if (tid == 0) n_blocks[g] = levels[g] = 0;
+    return;
+  }
+  const int na = clampi(n_lines_in[g], 1, ng);   // atoms = lines
+  int n2 = RB_MIN_SLOTS;
+  while (n2 < na) n2 <<= 1;                      // <= slots: a power of two >= 8 and >= ng >= na
+  unsigned long long* A = reinterpret_cast<unsigned long long*>(rb_lds);
+  unsigned long long* B = reinterpret_cast<unsigned long long*>(rb_lds + 8 * (size_t)slots);
+  int* Bi = reinterpret_cast<int*>(B);
+  unsigned* keys = reinterpret_cast<unsigned*>(rb_lds);
+  int* TY = reinterpret_cast<int*>(rb_lds + 4 * (size_t)slots);
+  int* TX = reinterpret_cast<int*>(rb_lds + 8 * (size_t)slots);
+  int* seg = reinterpret_cast<int*>(rb_lds + 12 * (size_t)slots);
+  int* part = reinterpret_cast<int*>(rb_lds + 16 * (size_t)slots);
+
+  // 1, 2. per axis: intervals -> per-line ends -> rank r and hr
+  int r_y[RD_OWN], r_x[RD_OWN], t_y[RD_OWN], t_x[RD_OWN];   // register arrays, constant indices
+#pragma unroll
+  for (int ax = 0; ax < 2; ++ax) {   // 0 = y, 1 = x
+    RB_FOR_OWN(k, a, n2) {
+      A[a] = RD_NONE;
+      B[a] = 0ull;
+    }
+    __syncthreads();
+    RB_FOR_OWN(k, i, ng) {
+      int x[16], y[16];
+      load_points(polys, g0 + i, grid, G.ax, G.ay, x, y);
+      int sx = 0, sy = 0, lo = ax ? x[0] : y[0], hi = lo;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        sx += x[15 - q] - x[q];
+        sy += y[15 - q] - y[q];
+      }
+#pragma unroll
+      for (int q = 1; q < 16; ++q) {
+        lo = min(lo, ax ? x[q] : y[q]);
+        hi = max(hi, ax ? x[q] : y[q]);
+      }
+      const int64_t m = (int64_t)(ax ? gap_x : gap_y) * max(abs(sx), abs(sy));   // < 10000 * 2^23 < 2^37
+      const int l = clampi(line_in[g0 + i], 0, na - 1);
+      atomicMin(&A[l], (unsigned long long)(16000ll * lo - m + RB_BIAS));   // in (0, 2^39)
+      atomicMax(&B[l], (unsigned long long)(16000ll * hi + m + RB_BIAS));
+    }
+    __syncthreads();
+    RB_FOR_OWN(k, a, na) A[a] = (min(A[a], (1ull << 39) - 1) << 13) | (unsigned long long)a;   // the own slot; pads stay RD_NONE
+    __syncthreads();
+    rb_sort(A, n2, tid);
+    RB_FOR_OWN(k, p, na) {
+      const int a = (int)(A[p] & 8191ull);
+      const unsigned long long hi = B[a];
+      int b0 = 0, b1 = na;                     // the first position whose lo exceeds hi = the number of atoms with lo <= hi
+      while (b0 < b1) {
+        const int mid = (b0 + b1) >> 1;
+        if ((A[mid] >> 13) <= hi) b0 = mid + 1; else b1 = mid;
+      }
+      if (ax) t_x[k] = (b0 << 13) | a; else t_y[k] = (b0 << 13) | a;
+    }
+    __syncthreads();   // hi has been read: region B becomes the ranks by atom
+    RB_FOR_OWN(k, p, na) Bi[(int)(A[p] & 8191ull)] = p;
+    __syncthreads();
+    RB_FOR_OWN(k, a, na) {
+      if (ax) r_x[k] = Bi[a]; else r_y[k] = Bi[a];
+    }
+    __syncthreads();
+  }
+
+  // 3. the levels
+  RB_FOR_OWN(k, p, na) {
+    TY[p] = t_y[k];
+    TX[p] = t_x[k];
+    seg[p] = 0;
+  }
+  __syncthreads();
+  const int p0 = 8 * tid;
+  int n_seg = 1, lv = 0, excl, total;
+  bool idle = false;
+  for (int l = 0; l < depth; ++l) {
+    const int* T = (l & 1) ? TX : TY;
+    RB_FOR_OWN(k, a, n2) keys[a] = a < na ? ((unsigned)seg[a] << 13) | (unsigned)((l & 1) ? r_x[k] : r_y[k]) : 0xffffffffu;
+    __syncthreads();
+    rb_sort(keys, n2, tid);
+    int s[8], r[8], at[8], v[8];
+    int run = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s[e] = r[e] = at[e] = 0;
+      if (p0 + e < na) {
+        const unsigned key = keys[p0 + e];
+        s[e] = (int)(key >> 13);
+        r[e] = (int)(key & 8191u);
+        const int tv = T[r[e]];
+        at[e] = tv & 8191;
+        run = max(run, (s[e] << 14) | (tv >> 13));   // hr <= 8192: 14 bits under the segment's 13
+      }
+      v[e] = run;                                    // inclusive inside the thread
+    }
+    rb_scan<true>(run, part, tid, &excl, &total);
+    int flags = 0, f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int prev = e ? max(excl, v[e - 1]) : excl;   // the maximum over everything in front of position p0 + e
+      f[e] = (p0 + e < na) && (p0 + e == 0 || (prev >> 14) != s[e] || r[e] >= (prev & 16383));
+      flags += f[e];
+    }
+    rb_scan<false>(flags, part, tid, &excl, &total);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      excl += f[e];
+      if (p0 + e < na) seg[at[e]] = excl - 1;
+    }
+    lv = l + 1;
+    const bool created = total > n_seg;   // block-uniform: every thread holds the same total
+    n_seg = total;
+    __syncthreads();                      // seg is complete
+    if (!created && idle) break;
+    idle = !created;
+  }
+
+  // 4. the new line numbers: the position of (segment, old line)
+  RB_FOR_OWN(k, a, n2) {
+    keys[a] = a < na ? ((unsigned)seg[a] << 13) | (unsigned)a : 0xffffffffu;
+    TY[a] = 0;   // the line's length, then its first rank
+  }
+  __syncthreads();
+  RB_FOR_OWN(k, i, ng) atomicAdd(&TY[clampi(line_in[g0 + i], 0, na - 1)], 1);
+  rb_sort(keys, n2, tid);   // its barriers also end the counting
+  // 5. the first rank of every line in the new order
+  int at[8], len[8], sum = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    at[e] = len[e] = 0;
+    if (p0 + e < na) {
+      at[e] = (int)(keys[p0 + e] & 8191u);
+      len[e] = TY[at[e]];
+      TX[at[e]] = p0 + e;
+    }
+    sum += len[e];
+  }
+  rb_scan<false>(sum, part, tid, &excl, &total);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    if (p0 + e < na) TY[at[e]] = excl;   // the slot this thread alone has read
+    excl += len[e];
+  }
+  __syncthreads();
+  RB_FOR_OWN(k, i, ng) {
+    const int l = clampi(line_in[g0 + i], 0, na - 1);
+    block[g0 + i] = seg[l];
+    line[g0 + i] = TX[l];
+    rank[g0 + i] = TY[l] + pos_in[g0 + i];
+  }
+  if (tid == 0) {
+    n_blocks[g] = n_seg;
+    levels[g] = lv;
+  }
+}
+
 }  // namespace
 
 extern "C" int omp_reading_links(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid, int gap, int back,
@@ -364,5 +608,25 @@ extern "C" int omp_reading_lines(const int32_t* polys, int n, const int32_t* tab
   hipLaunchKernelGGL(kern, dim3((unsigned)n_groups), dim3(RD_THREADS), 16 * (size_t)cap + 16, (hipStream_t)s, polys, n, tables, n_groups, cap, grid, succ0, cost0,
                      succ, pred, line, line_pos, rank, n_lines);
   OMP_CHECK_LAUNCH("omp_reading_lines");
+  return OMP_OK;
+}
+
+extern "C" int omp_reading_blocks(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid, int gap_x,
+                                  int gap_y, int depth, const int32_t* line_in, const int32_t* line_pos_in, const int32_t* n_lines_in, int32_t* block,
+                                  int32_t* line, int32_t* rank, int32_t* n_blocks, int32_t* levels, omp_stream_t s) {
+  int max_group = 0;
+  if (const int rc = reading_check("omp_reading_blocks", polys, n, tables, host_tables, n_groups, grid, &max_group)) return rc;
+  OMP_CHECK_ARG(gap_x >= 0 && gap_x <= RD_MAX_PARAM && gap_y >= 0 && gap_y <= RD_MAX_PARAM, "omp_reading_blocks: gap_x %d, gap_y %d permille (0 .. %d)", gap_x,
+                gap_y, RD_MAX_PARAM);
+  OMP_CHECK_ARG(depth >= 1 && depth <= RB_MAX_DEPTH, "omp_reading_blocks: depth %d (1 .. %d)", depth, RB_MAX_DEPTH);
+  if (n == 0) return OMP_OK;
+  OMP_CHECK_ARG(line_in && line_pos_in && n_lines_in && block && line && rank && n_blocks && levels, "omp_reading_blocks: null pointer");
+  int slots = RB_MIN_SLOTS;
+  while (slots < max_group && slots < RD_MAX_GROUP) slots <<= 1;   // a larger group is refused on the device
+  constexpr auto kern = reading_blocks_kernel;
+  if (const int rc = omp_raise_lds<kern>("omp_reading_blocks")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)n_groups), dim3(RD_THREADS), 16 * (size_t)slots + RB_EXTRA, (hipStream_t)s, polys, n, tables, n_groups, slots, grid,
+                     gap_x, gap_y, depth, line_in, line_pos_in, n_lines_in, block, line, rank, n_blocks, levels);
+  OMP_CHECK_LAUNCH("omp_reading_blocks");
   return OMP_OK;
 }

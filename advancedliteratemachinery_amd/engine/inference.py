@@ -117,7 +117,7 @@ def _n_images(images):
 @torch.no_grad()
 def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None,
             windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou', suppress_order='first',
-            reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5):
+            reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
     """images: list of (3,H,W) tensors, a (B,3,H,W) tensor or a NestedTensor (this package's or the reference's).
     Returns one entry per image: list of records (text spotting), list of tuples (KIE) or [].
     ragged=False: images of different sizes are padded to the largest and masked, and an image's tokens may then depend on the
@@ -144,10 +144,19 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     frames), the lines are ordered top to bottom, every record gains `line` and `line_pos`, and each image's list is reordered
     accordingly (utils.reading.page_lines joins it into strings).  It runs on the raw polygon ids on the device, ONE device call for
     all images, after suppress= (on the survivors) and before lexicon=; `merged` indices keep counting the records before suppression.
-    Without reading_order the records are the plain call's."""
+    Without reading_order the records are the plain call's.
+    blocks=True (needs reading_order=True), block_gap_x, block_gap_y (floats in [0, 10], in units of a word's height), block_depth (1 ..
+    16): multi-column pages (utils/reading.py: blocks_cpu) -- a recursive XY-cut over the lines, in the same
+    device call, directly after the lines: the page is cut into bands wherever a horizontal gap wider than block_gap_y heights
+    crosses it, every band into columns at vertical gaps wider than block_gap_x heights, and so on, block_depth levels at most.
+    Every record gains `block` (its block within the image, in reading order from 0), `line` counts up through block 0, then block
+    1, ..., `line_pos` stays, and each image's list comes in that order (utils.reading.page_blocks gives one string per block).  The
+    two gap defaults are choices that no data set has tested.  Without blocks no new code runs."""
+    if blocks and not reading_order:
+        raise ValueError('blocks=True orders the lines of reading_order=True: pass both')
     if reading_order:
         from ..utils import reading as RD
-        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie, blocks, block_gap_x, block_gap_y, block_depth)
     if suppress is not None:
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
@@ -187,7 +196,8 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
                                   device=next(model.parameters()).device, kept_rows=rows)
     if reading_order:
         out = RD.order_records(out, [None if r is None else r[0][1] for r in raw], sizes, args.num_bins, line_gap, line_back, line_offset, rows=rows,
-                               device=next(model.parameters()).device)
+                               device=next(model.parameters()).device, blocks=blocks, block_gap_x=block_gap_x, block_gap_y=block_gap_y,
+                               block_depth=block_depth)
     if lexicon is not None:
         from ..utils import lexicon as LX
         matcher = LX.resolve_lexicon(lexicon, len(out), next(model.parameters()).device, args.chars)
@@ -198,7 +208,8 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
 @torch.no_grad()
 def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
                    lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou',
-                   suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5):
+                   suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5, blocks=False, block_gap_x=1.0,
+                   block_gap_y=1.5, block_depth=8):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
@@ -209,6 +220,7 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     suppress, suppress_measure, suppress_order: as predict (overlap suppression; survivors gain `merged`).
     reading_order, line_gap, line_back, line_offset: as predict (records gain `line`, `line_pos` and come in reading order); the
     aspect of every image is that of the ORIGINAL image, whose size scales the polygons.
+    blocks, block_gap_x, block_gap_y, block_depth: as predict (records gain `block`; needs reading_order=True).
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
     if lexicon is not None and args.infer_vie:
@@ -218,10 +230,14 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
         skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
+    if blocks and not reading_order:
+        raise ValueError('blocks=True orders the lines of reading_order=True: pass both')
     if reading_order:
         from ..utils import reading as RD
-        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie, blocks, block_gap_x, block_gap_y, block_depth)
         skw.update(reading_order=True, line_gap=line_gap, line_back=line_back, line_offset=line_offset)
+        if blocks:
+            skw.update(blocks=True, block_gap_x=block_gap_x, block_gap_y=block_gap_y, block_depth=block_depth)
     dev = next(model.parameters()).device
     if preprocessor is None:
         preprocessor = DevicePreprocessor(args.test_min_size, args.test_max_size, dev)

@@ -55,7 +55,7 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
                        lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
                        grid=None, suppress=None, suppress_measure='iou', suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5,
-                       line_offset=0.5):
+                       line_offset=0.5, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -75,6 +75,9 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     reading_order, line_gap, line_back, line_offset: reading order, as predict_images takes it: the records are
     put into text lines and reading order BEFORE the crops, so the crops are read in that order and `mgp_*` land on the reordered
     records; utils.reading.page_lines(records, field='mgp_text') joins an image's lines.
+    blocks, block_gap_x, block_gap_y, block_depth: multi-column pages, as predict_images takes them (needs
+    reading_order=True): the records gain `block` and come block by block BEFORE the crops, so `mgp_*` land on the reordered records;
+    utils.reading.page_blocks(records, field='mgp_text') gives one string per block.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
@@ -85,10 +88,14 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
         from ..utils import overlap as OV
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
         skw = dict(suppress=suppress, suppress_measure=suppress_measure, suppress_order=suppress_order)
+    if blocks and not reading_order:
+        raise ValueError('blocks=True orders the lines of reading_order=True: pass both')
     if reading_order:
         from ..utils import reading as RD
-        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie)
+        RD.check_reading_args(line_gap, line_back, line_offset, args.infer_vie, blocks, block_gap_x, block_gap_y, block_depth)
         skw.update(reading_order=True, line_gap=line_gap, line_back=line_back, line_offset=line_offset)
+        if blocks:
+            skw.update(blocks=True, block_gap_x=block_gap_x, block_gap_y=block_gap_y, block_depth=block_depth)
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
     if lexicon is not None:

@@ -797,3 +797,25 @@ def reading_lines(polys, tables, host_tables, n_groups, grid, succ0, cost0, out=
 def split_reading_ints(ints, n):
     """the int32 tensor of reading_lines (on either side of the copy) -> (succ, pred, line, line_pos, rank, n_lines)"""
     return tuple(ints[k * n:(k + 1) * n] for k in range(5)) + (ints[5 * n:],)
+
+
+def reading_blocks(polys, tables, host_tables, n_groups, grid, lines, gap_x, gap_y, depth, out=None):
+    """omp_reading_blocks (utils/reading.py: blocks_cpu is the specification): the XY-cut over the lines.  lines: reading_lines' int32
+    tensor [5 N + G], on the device.  -> ONE int32 tensor [3 N + 2 G] = block | line | rank | n_blocks | levels (split_block_ints)."""
+    N, G, host = _reading_tables(polys, tables, host_tables, n_groups)
+    if not lines.is_cuda or lines.dtype != torch.int32 or not lines.is_contiguous() or lines.numel() != 5 * N + G:
+        raise ValueError('lines must be the contiguous device int32 tensor of reading_lines with %d elements' % (5 * N + G))
+    if out is None:
+        out = torch.empty(3 * N + 2 * G, dtype=torch.int32, device=polys.device)
+    elif out.dtype != torch.int32 or out.numel() != 3 * N + 2 * G or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor with %d elements' % (3 * N + 2 * G))
+    rc = _lib.lib().omp_reading_blocks(ptr(polys), N, ptr(tables), host.ctypes.data, G, int(grid), int(gap_x), int(gap_y), int(depth),
+                                       ptr(lines[2 * N:3 * N]), ptr(lines[3 * N:4 * N]), ptr(lines[5 * N:]), ptr(out[:N]), ptr(out[N:2 * N]),
+                                       ptr(out[2 * N:3 * N]), ptr(out[3 * N:3 * N + G]), ptr(out[3 * N + G:]), stream())
+    _lib.check(rc, 'omp_reading_blocks')
+    return out
+
+
+def split_block_ints(ints, n, n_groups):
+    """the int32 tensor of reading_blocks (on either side of the copy) -> (block, line, rank, n_blocks, levels)"""
+    return tuple(ints[k * n:(k + 1) * n] for k in range(3)) + (ints[3 * n:3 * n + n_groups], ints[3 * n + n_groups:])

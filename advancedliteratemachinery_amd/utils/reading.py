@@ -30,8 +30,25 @@ Cycles     a cycle is cut in front of its lowest-index member: that member's pre
 Lines      a line is a path; line_pos = distance from the head.  Lines of a group are ordered by the mean of C_y over their members
            (compared exactly: sum_1 count_2 against sum_2 count_1), then L_x of the head, then the head's index; numbered from 0.
            rank = the word's position in its group with the lines concatenated in that order.
-Not done   multi-column layout analysis: two columns at the same height interleave line by line.  Lines are ordered by y only, so
-           a page of vertical lines is grouped correctly and ordered by the lines' mean y, then by the heads' x.
+Blocks     blocks_cpu, behind `blocks=True`: a recursive XY-cut over the LINES, level-synchronous.  Per word, on the
+           scaled points: the bounding box x0, x1, y0, y1 (min / max over the 16 points), s = sum_k (B[k] - T[k]) (8 * the mean height
+           vector), t = max(|s_x|, |s_y|); the inflated intervals, in 1 / 16000 of a scaled bin (8 of s, 1000 of permille, 2 for half a
+           gap on each side): X = [16000 x0 - gap_x t, 16000 x1 + gap_x t], Y the same with gap_y.  Two words are apart on an axis
+           exactly when their raw gap exceeds gap / 1000 times the mean of their two heights.  |16000 x| < 2^34, t < 2^23,
+           gap t < 2^37: every end stays below 2^38 in magnitude (asserted).  The atoms are the lines: an atom's interval is the min of
+           the lower and the max of the upper ends of its words; a line is never cut.  All atoms of a group start in segment 0.  Level
+           l = 0, 1, ... works on y when l is even (bands first) and on x when l is odd: inside every segment the atoms are walked in
+           (lo, line number) order and an atom starts a new component when its lo is STRICTLY greater than the running maximum of hi
+           over the atoms before it in its segment; components numbered in (old segment, position) order are the new segments, so
+           segment numbers are always in reading order.  Stop after `depth` levels, or as soon as two consecutive levels created no
+           new segment (neither axis cuts anything any more).  block = the final segment of the word's line; line = the position of
+           (block, old line) in sorted order; rank = the position with the lines concatenated in the new order; n_blocks per group;
+           levels = the levels actually run (0 for a group without words).
+Not done   L-shaped regions are not cut (XY-cut only finds gaps that cross a whole segment).  A line that the linker joined across a
+           gutter holds its two columns in one block: the remedy is a smaller line_gap.  Without blocks, lines are ordered by y only:
+           two columns at the same height interleave line by line; a page of vertical lines is grouped correctly and ordered by the
+           lines' mean y, then by the heads' x.  The defaults block_gap_x = 1.0 and block_gap_y = 1.5 are choices that no data set
+           has tested; no accuracy is claimed.
 """
 import functools
 
@@ -42,6 +59,8 @@ from .overlap import GRID_MAX, GROUP_MAX, _check_grid, _check_groups, _check_pol
 ASPECT_MAX = 256
 PARAM_MAX = 10000
 DEFAULTS = dict(gap=2000, back=500, offset=500)
+DEPTH_MAX = 16
+BLOCK_DEFAULTS = dict(gap_x=1000, gap_y=1500, depth=8)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -223,13 +242,109 @@ def lines_cpu(polys, group_start, aspect, gap=2000, back=500, offset=500, grid=G
     succ0, cost0 = links_cpu(p, gs, asp, gap, back, offset, grid)
     return resolve_cpu(succ0, cost0, gs, features_cpu(p, _aspect_per_word(gs, asp)))
 
+def _check_block_params(gap_x, gap_y, depth):
+    out = []
+    for name, v in (('gap_x', gap_x), ('gap_y', gap_y)):
+        if int(v) != v or int(v) < 0 or int(v) > PARAM_MAX:
+            raise ValueError('%s is a permille parameter 0 .. %d, got %r' % (name, PARAM_MAX, v))
+        out.append(int(v))
+    if isinstance(depth, bool) or int(depth) != depth or int(depth) < 1 or int(depth) > DEPTH_MAX:
+        raise ValueError('depth is an integer 1 .. %d, got %r' % (DEPTH_MAX, depth))
+    return out[0], out[1], int(depth)
+
+
+def intervals_cpu(polys, aspect_per_word, gap_x, gap_y):
+    """-> the inflated intervals of every word, int64 [N] each: (x_lo, x_hi, y_lo, y_hi), in 1 / 16000 of a scaled bin"""
+    p = np.asarray(polys, dtype=np.int64).reshape(-1, 32)
+    a = np.asarray(aspect_per_word, dtype=np.int64).reshape(-1, 2)
+    assert p.shape[0] == a.shape[0], 'one aspect per word'
+    assert p.size == 0 or (p.min() >= 0 and p.max() <= GRID_MAX - 1 and a.min() >= 1 and a.max() <= ASPECT_MAX), 'bins 0 .. 4095, aspects 1 .. 256'
+    assert 0 <= gap_x <= PARAM_MAX and 0 <= gap_y <= PARAM_MAX
+    P = p.reshape(-1, 16, 2) * a[:, None, :]
+    s = (P[:, :7:-1] - P[:, :8]).sum(1)                      # sum_k (B[k] - T[k]), B[k] = P[15 - k]
+    t = np.abs(s).max(1) if len(P) else np.zeros(0, np.int64)
+    lo, hi = P.min(1), P.max(1)
+    out = (16000 * lo[:, 0] - gap_x * t, 16000 * hi[:, 0] + gap_x * t, 16000 * lo[:, 1] - gap_y * t, 16000 * hi[:, 1] + gap_y * t)
+    assert p.size == 0 or (t.max() < 2 ** 23 and max(int(np.abs(v).max()) for v in out) < 2 ** 38), 'the bounds of the docstring'
+    return out
+
+
+def blocks_cpu(polys, group_start, aspect, line, line_pos, n_lines, gap_x=1000, gap_y=1500, depth=8, grid=GRID_MAX):
+    """The XY-cut of the docstring over the lines of lines_cpu (its `line`, `line_pos`, `n_lines`; line_pos places a word inside its
+    line, which no cut changes).  -> dict(block, line, rank: int32 [N]; n_blocks, levels: int32 [G])"""
+    grid = _check_grid(grid)
+    p = _check_polys(polys, grid)
+    gs = _check_groups(group_start, len(p))
+    asp = _check_aspect(aspect, gs.size - 1)
+    gap_x, gap_y, depth = _check_block_params(gap_x, gap_y, depth)
+    N, G = len(p), gs.size - 1
+    line = np.asarray(line, dtype=np.int64).reshape(-1)
+    line_pos = np.asarray(line_pos, dtype=np.int64).reshape(-1)
+    n_lines = np.asarray(n_lines, dtype=np.int64).reshape(-1)
+    if line.size != N or line_pos.size != N or n_lines.size != G:
+        raise ValueError('line, line_pos are per word (%d) and n_lines per group (%d)' % (N, G))
+    xl, xh, yl, yh = intervals_cpu(p, _aspect_per_word(gs, asp), gap_x, gap_y)
+    block = np.zeros(N, dtype=np.int32)
+    new_line = np.zeros(N, dtype=np.int32)
+    rank = np.zeros(N, dtype=np.int32)
+    n_blocks = np.zeros(G, dtype=np.int32)
+    levels = np.zeros(G, dtype=np.int32)
+    big = np.int64(2 ** 62)
+    for g in range(G):
+        w0, w1 = int(gs[g]), int(gs[g + 1])
+        n = int(n_lines[g])
+        if w1 == w0:
+            if n != 0:
+                raise ValueError('group %d has no words and %d lines' % (g, n))
+            continue
+        ln = line[w0:w1]
+        count = np.bincount(ln[(ln >= 0) & (ln < n)], minlength=max(n, 1))[:max(n, 1)]
+        if n < 1 or ln.min() < 0 or ln.max() >= n or (count == 0).any():
+            raise ValueError('group %d: its words must fill the lines 0 .. n_lines - 1' % g)
+        ends = {}
+        for name, v, red, init in (('xl', xl, np.minimum, big), ('xh', xh, np.maximum, -big), ('yl', yl, np.minimum, big), ('yh', yh, np.maximum, -big)):
+            ends[name] = np.full(n, init, dtype=np.int64)
+            red.at(ends[name], ln, v[w0:w1])
+        seg = np.zeros(n, dtype=np.int64)
+        n_seg, idle, lv = 1, False, 0
+        for lv in range(1, depth + 1):
+            lo, hi = (ends['yl'], ends['yh']) if lv % 2 else (ends['xl'], ends['xh'])    # level lv - 1: even levels cut y
+            order = np.lexsort((np.arange(n), lo, seg))                                    # (segment, lo, line number)
+            new = np.zeros(n, dtype=np.int64)
+            comp, top, last = -1, 0, -1
+            for a in order.tolist():
+                if seg[a] != last or lo[a] > top:
+                    comp += 1
+                    top = hi[a]
+                    last = seg[a]
+                else:
+                    top = max(top, hi[a])
+                new[a] = comp
+            created = comp + 1 > n_seg
+            seg, n_seg = new, comp + 1
+            if not created and idle:
+                break
+            idle = not created
+        order = np.lexsort((np.arange(n), seg))                                            # (block, old line)
+        pos = np.empty(n, dtype=np.int64)
+        pos[order] = np.arange(n)
+        start = np.zeros(n, dtype=np.int64)
+        start[order] = np.concatenate([[0], np.cumsum(count[order])[:-1]])
+        block[w0:w1] = seg[ln]
+        new_line[w0:w1] = pos[ln]
+        rank[w0:w1] = start[ln] + line_pos[w0:w1]
+        n_blocks[g], levels[g] = n_seg, lv
+    return dict(block=block, line=new_line, rank=rank, n_blocks=n_blocks, levels=levels)
+
 
 # ---------------------------------------------------------------------------------------------
 # the device stage
 # ---------------------------------------------------------------------------------------------
 class ReadingOrder(object):
     """lines_cpu on the device.  A call packs group_start and aspect into ONE upload, runs omp_reading_links and omp_reading_lines on
-    the current stream and downloads the int32 outputs in ONE copy.  There is no CPU fallback: lines_cpu is the host specification."""
+    the current stream and downloads the int32 outputs in ONE copy.  There is no CPU fallback: lines_cpu is the host specification.
+    With blocks=(gap_x, gap_y, depth) a third launch, omp_reading_blocks, follows on the same stream and tables, and the same ONE
+    download also carries blocks_cpu's outputs."""
 
     def __init__(self, device, grid):
         import torch
@@ -239,12 +354,15 @@ class ReadingOrder(object):
                                'lines_cpu is the host specification' % (self.device,))
         self.grid = _check_grid(grid)
 
-    def run(self, polys, group_start, aspect, gap=2000, back=500, offset=500, want_links=False):
-        """polys: int32 / int64 [N, 32] on the device or the host -> lines_cpu's dict as numpy (plus succ0, cost0 when want_links)"""
+    def run(self, polys, group_start, aspect, gap=2000, back=500, offset=500, want_links=False, blocks=None):
+        """polys: int32 / int64 [N, 32] on the device or the host -> lines_cpu's dict as numpy (plus succ0, cost0 when want_links).
+        blocks: None, or (gap_x, gap_y, depth) of blocks_cpu: the dict gains `blocks`, blocks_cpu's dict on this call's lines."""
         import torch
 
         from .. import ops
         gap, back, offset = _check_params(gap, back, offset)
+        if blocks is not None:
+            blocks = _check_block_params(*blocks)
         polys = torch.as_tensor(polys)
         if polys.dim() != 2 or polys.shape[1] != 32:
             raise ValueError('polys must be [N, 32], got %s' % (tuple(polys.shape),))
@@ -259,43 +377,73 @@ class ReadingOrder(object):
             out = dict(succ=z, pred=z.copy(), line=z.copy(), line_pos=z.copy(), rank=z.copy(), n_lines=np.zeros(G, np.int32))
             if want_links:
                 out.update(succ0=z.copy(), cost0=np.zeros(0, np.int64))
+            if blocks is not None:
+                out['blocks'] = dict(block=z.copy(), line=z.copy(), rank=z.copy(), n_blocks=np.zeros(G, np.int32), levels=np.zeros(G, np.int32))
             return out
         host = np.concatenate([gs.astype(np.int32), asp.reshape(-1)]).astype(np.int32)
         with torch.cuda.device(self.device):
             tables = torch.from_numpy(host).to(self.device)                   # the one upload
             d_polys = polys.to(self.device).clamp(-1, GRID_MAX).to(torch.int32).contiguous()
             succ0, cost0 = ops.reading_links(d_polys, tables, host, G, self.grid, gap, back, offset)
-            ints = ops.reading_lines(d_polys, tables, host, G, self.grid, succ0, cost0)
+            if blocks is None:
+                ints = ops.reading_lines(d_polys, tables, host, G, self.grid, succ0, cost0)
+            else:                                                             # one tensor behind both launches: still one download
+                ints = torch.empty(8 * N + 3 * G, dtype=torch.int32, device=self.device)
+                ops.reading_lines(d_polys, tables, host, G, self.grid, succ0, cost0, out=ints[:5 * N + G])
+                ops.reading_blocks(d_polys, tables, host, G, self.grid, ints[:5 * N + G], *blocks, out=ints[5 * N + G:])
             h = ints.cpu().numpy()                                            # the one download
-            out = dict(zip(('succ', 'pred', 'line', 'line_pos', 'rank'), (h[k * N:(k + 1) * N].copy() for k in range(5))), n_lines=h[5 * N:].copy())
+            out = dict(zip(('succ', 'pred', 'line', 'line_pos', 'rank'), (h[k * N:(k + 1) * N].copy() for k in range(5))), n_lines=h[5 * N:5 * N + G].copy())
+            if blocks is not None:
+                b = h[5 * N + G:]
+                out['blocks'] = dict(zip(('block', 'line', 'rank'), (b[k * N:(k + 1) * N].copy() for k in range(3))), n_blocks=b[3 * N:3 * N + G].copy(),
+                                     levels=b[3 * N + G:].copy())
             if want_links:
                 out.update(succ0=succ0.cpu().numpy(), cost0=cost0.cpu().numpy())
         if (out['n_lines'] < 0).any():
             raise RuntimeError('omp_reading_lines refused a group (more than %d words)' % GROUP_MAX)
+        if blocks is not None and (out['blocks']['n_blocks'] < 0).any():
+            raise RuntimeError('omp_reading_blocks refused a group (more than %d words)' % GROUP_MAX)
         return out
 
-    def __call__(self, polys, group_start, aspect, gap=2000, back=500, offset=500):
-        return self.run(polys, group_start, aspect, gap, back, offset)
+    def __call__(self, polys, group_start, aspect, gap=2000, back=500, offset=500, blocks=None):
+        return self.run(polys, group_start, aspect, gap, back, offset, blocks=blocks)
 
 
 # ---------------------------------------------------------------------------------------------
 # the engine's side: `reading_order=` of predict / predict_images / spot_and_recognize
 # ---------------------------------------------------------------------------------------------
-def check_reading_args(line_gap=2.0, line_back=0.5, line_offset=0.5, infer_vie=False):
-    """the refusals of the public interface -> (gap, back, offset) in permille"""
+def check_block_args(blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8, reading_order=True, infer_vie=False):
+    """the refusals of `blocks=` -> None without it, else (gap_x, gap_y) in permille and the depth"""
+    if not blocks:
+        return None
+    if infer_vie:
+        raise ValueError('blocks= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+    if not reading_order:
+        raise ValueError('blocks=True orders the lines of reading_order=True: pass both')
+    return _check_block_params(permille(block_gap_x, 'block_gap_x'), permille(block_gap_y, 'block_gap_y'), block_depth)
+
+
+def check_reading_args(line_gap=2.0, line_back=0.5, line_offset=0.5, infer_vie=False, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
+    """the refusals of the public interface -> (gap, back, offset) in permille; the block arguments are checked when blocks is set
+    (check_block_args converts them)"""
     if infer_vie:
         raise ValueError('reading_order= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+    check_block_args(blocks, block_gap_x, block_gap_y, block_depth)
     return permille(line_gap, 'line_gap'), permille(line_back, 'line_back'), permille(line_offset, 'line_offset')
 
 
-def order_records(records, raw_polys, sizes, grid, line_gap=2.0, line_back=0.5, line_offset=0.5, rows=None, reader=None, device=None):
+def order_records(records, raw_polys, sizes, grid, line_gap=2.0, line_back=0.5, line_offset=0.5, rows=None, reader=None, device=None, blocks=False,
+                  block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
     """records: per image the list of record dicts.  raw_polys: per image the polygon decoder's ids ([n_b, 32] tensors, None or empty
     for an image without records), on the device; rows: per image the rows of raw_polys its records stand for (None: all of them, in
     order -- after suppress= the survivors').  sizes: per image (h, w), the orig_size the polygons were scaled by.  One device call for
     all images (`reader`: a ReadingOrder, or anything with its __call__; default: one on `device`).
-    -> the lists reordered by rank; every record gains `line` and `line_pos`."""
+    -> the lists reordered by rank; every record gains `line` and `line_pos`.  blocks=True (block_gap_x, block_gap_y, block_depth): the
+    same call also cuts the lines into blocks (blocks_cpu); every record gains `block`, `line` counts through the blocks and the lists
+    come in the blocks' order."""
     import torch
     gap, back, offset = check_reading_args(line_gap, line_back, line_offset)
+    cut = check_block_args(blocks, block_gap_x, block_gap_y, block_depth)
     counts = [len(r) for r in records]
     gs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     if int(gs[-1]) == 0:
@@ -314,14 +462,21 @@ def order_records(records, raw_polys, sizes, grid, line_gap=2.0, line_back=0.5, 
     aspect = np.asarray([aspect_of(*sizes[b]) for b in range(len(records))], dtype=np.int32).reshape(-1, 2)
     if reader is None:
         reader = ReadingOrder(polys.device if device is None else device, grid)
-    res = reader(polys, gs, aspect, gap, back, offset)
+    if cut is None:
+        res = reader(polys, gs, aspect, gap, back, offset)
+        line, rank = res['line'], res['rank']
+    else:
+        res = reader(polys, gs, aspect, gap, back, offset, blocks=cut)
+        line, rank = res['blocks']['line'], res['blocks']['rank']
     out = []
     for b, recs in enumerate(records):
         lo = int(gs[b])
         ordered = [None] * len(recs)
         for i, r in enumerate(recs):
-            r['line'], r['line_pos'] = int(res['line'][lo + i]), int(res['line_pos'][lo + i])
-            ordered[int(res['rank'][lo + i])] = r
+            r['line'], r['line_pos'] = int(line[lo + i]), int(res['line_pos'][lo + i])
+            if cut is not None:
+                r['block'] = int(res['blocks']['block'][lo + i])
+            ordered[int(rank[lo + i])] = r
         out.append(ordered)
     return out
 
@@ -336,3 +491,15 @@ def page_lines(records, field='rec', sep=' '):
             last = r['line']
         lines[-1].append(str(r[field]))
     return [sep.join(l) for l in lines]
+
+
+def page_blocks(records, field='rec', sep=' ', line_sep='\n'):
+    """one image's records of a blocks=True call -> one string per block: the block's lines (page_lines) joined by line_sep"""
+    blocks = []
+    last = None
+    for r in records:
+        if r['block'] != last:
+            blocks.append([])
+            last = r['block']
+        blocks[-1].append(r)
+    return [line_sep.join(page_lines(b, field, sep)) for b in blocks]

@@ -703,6 +703,24 @@ int omp_reading_links(const int32_t* polys, int n, const int32_t* tables, const 
 int omp_reading_lines(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid,
                       const int32_t* succ0, const int64_t* cost0, int32_t* succ, int32_t* pred, int32_t* line, int32_t* line_pos,
                       int32_t* rank, int32_t* n_lines, omp_stream_t s);
+/* Blocks: a recursive XY-cut over omp_reading_lines' lines, for multi-column pages.  Neither reference project has
+ * layout analysis; utils/reading.py::blocks_cpu is the specification and every output integer equals it.  Stands for: blocks_cpu.
+ *   gap_x, gap_y  permille of a word's height, 0 .. 10000; depth 1 .. 16: the number of levels at most
+ *   line_in, line_pos_in int32 [n], n_lines_in int32 [n_groups]: omp_reading_lines' line, line_pos and n_lines, on the device
+ *   per word, on the scaled points: the bounding box, s = sum_k (B[k] - T[k]), t = max(|s_x|, |s_y|), the inflated intervals
+ *               [16000 x0 - gap_x t, 16000 x1 + gap_x t] and the same on y with gap_y (below 2^38 in magnitude); a line's interval is the
+ *               min / max over its words.  Level l cuts y (l even) or x (l odd): inside every segment, in (lo, line) order, a line starts
+ *               a new component when its lo is strictly greater than the largest hi in front of it; components numbered in (segment,
+ *               position) order are the new segments.  Stops after depth levels or after two levels in a row that created none.
+ *   block, line, rank int32 [n]: the word's block in its group (reading order from 0), its line renumbered through the blocks, its
+ *               position with the lines concatenated in the new order;  n_blocks, levels int32 [n_groups]: blocks per group and levels
+ *               run (0, 0 for a group without words); n_blocks = -1 for a group that is REFUSED on the device (more than 8192 words),
+ *               of which nothing else is written
+ * One launch, one workgroup of 1024 threads per group, everything in LDS (a bitonic sort and scans per level); no allocation and no
+ * synchronisation.  n == 0 returns OMP_OK without a launch. */
+int omp_reading_blocks(const int32_t* polys, int n, const int32_t* tables, const int32_t* host_tables, int n_groups, int grid, int gap_x,
+                       int gap_y, int depth, const int32_t* line_in, const int32_t* line_pos_in, const int32_t* n_lines_in, int32_t* block,
+                       int32_t* line, int32_t* rank, int32_t* n_blocks, int32_t* levels, omp_stream_t s);
 
 #ifdef __cplusplus
 }
