@@ -129,6 +129,8 @@ _SIGS = {
     'omp_debug_cross_q4': (c_int, [c_int]),
     'omp_debug_cross_nt': (c_int, [c_int]),
     'omp_debug_self_attn_impl': (c_int, [c_int]),
+    'omp_debug_fused_self_attn': (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 6 + [c_int, c_int, c_void_p, c_int] + [c_void_p] * 5 +
+                                  [c_int, c_void_p]),
     'omp_debug_sample_impl': (c_int, [c_int]),
     'omp_debug_dec_fused': (c_int, [c_int]),
     'omp_vit_patch_embed': (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),

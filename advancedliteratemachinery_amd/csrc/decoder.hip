@@ -1540,7 +1540,8 @@ extern "C" int omp_dec_self_attn_step(const void* qkv, void* kcache, void* vcach
                                       const int32_t* d_pos, int dtype, int R, int nH, int d, int Lmax,
                                       omp_stream_t s) {
   OMP_CHECK_ARG(qkv && kcache && vcache && out && d_pos, "omp_dec_self_attn_step: null pointer");
-  OMP_CHECK_ARG(d == nH * DH, "omp_dec_self_attn_step: head_dim must be 64 (d=%d nH=%d)", d, nH);
+  OMP_CHECK_ARG(R > 0 && Lmax > 0, "omp_dec_self_attn_step: R and Lmax must be positive (R=%d Lmax=%d)", R, Lmax);
+  OMP_CHECK_ARG(nH > 0 && d == nH * DH, "omp_dec_self_attn_step: head_dim must be 64 (d=%d nH=%d)", d, nH);
   OMP_CHECK_ARG(dtype == OMP_F32 || dtype == OMP_BF16, "omp_dec_self_attn_step: bad dtype");
   // many rows, short caches (polygon / recognition): one wave per row; few rows, long caches (points): one wave per (row, head)
   const int impl = omp_cur().self_attn_impl;
@@ -1743,6 +1744,15 @@ bool fused_step_ok(const omp_decoder_plan* P) {
   return omp_cur().dec_fused != 1 && P->pre_norm && P->dtype == OMP_BF16 && P->d_model == 512 && P->n_heads == 8 && P->R <= fused_sa_max_rows();
 }
 
+// the one launch of dec_fused_self_attn_kernel: the engine (launch_fused_self_attn) and omp_debug_fused_self_attn both end here
+int launch_fused_sa(const FusedSaP& fp, bool embed, hipStream_t st) {
+  const dim3 grid((fp.R + 3) / 4, 8);   // the kernel is built for d = 512: 8 heads of 64
+  if (embed) hipLaunchKernelGGL((dec_fused_self_attn_kernel<true, 4>), grid, dim3(256), 0, st, fp);
+  else hipLaunchKernelGGL((dec_fused_self_attn_kernel<false, 4>), grid, dim3(256), 0, st, fp);
+  OMP_CHECK_LAUNCH("omp_decoder_run(fused self-attention)");
+  return OMP_OK;
+}
+
 int launch_fused_self_attn(const omp_decoder_plan* P, const omp_dec_layer& L, bool embed, hipStream_t st) {
   FusedSaP fp;
   fp.x = P->x; fp.ln_g = L.n1_g; fp.ln_b = L.n1_b; fp.eps = P->eps;
@@ -1751,11 +1761,7 @@ int launch_fused_self_attn(const omp_decoder_plan* P, const omp_dec_layer& L, bo
   fp.out = reinterpret_cast<bf16_t*>(P->att); fp.d_pos = P->d_pos; fp.R = P->R; fp.Lmax = P->Lmax;
   fp.seq = P->seq; fp.seq_ld = P->seq_ld; fp.word = P->word_emb; fp.pos_tab = P->pos_tab; fp.emb_g = P->emb_g; fp.emb_b = P->emb_b;
   fp.x_out = P->x;
-  const dim3 grid((P->R + 3) / 4, P->n_heads);
-  if (embed) hipLaunchKernelGGL((dec_fused_self_attn_kernel<true, 4>), grid, dim3(256), 0, st, fp);
-  else hipLaunchKernelGGL((dec_fused_self_attn_kernel<false, 4>), grid, dim3(256), 0, st, fp);
-  OMP_CHECK_LAUNCH("omp_decoder_run(fused self-attention)");
-  return OMP_OK;
+  return launch_fused_sa(fp, embed, st);
 }
 
 // fp32 self-attention step of the many-row kernel writing SPLIT PAIRS (the parity engine's chains): omp_dec_self_attn_step + omp_split_bf16 in one launch
@@ -1990,6 +1996,29 @@ extern "C" int omp_debug_sample_impl(int which) {
 extern "C" int omp_debug_self_attn_impl(int which) {
   omp_cur().self_attn_impl = (which == 1 || which == 2) ? which : 0;
   return OMP_OK;
+}
+
+extern "C" int omp_debug_fused_self_attn(const float* x, const float* ln_g, const float* ln_b, float eps, const void* W,
+                                         const float* bias_tab, void* kcache, void* vcache, void* out, const int32_t* d_pos,
+                                         int R, int Lmax, const int32_t* seq, int seq_ld, const float* word_emb,
+                                         const float* pos_tab, const float* emb_g, const float* emb_b, float* x_out, int embed,
+                                         omp_stream_t s) {
+  OMP_CHECK_ARG(ln_g && ln_b && W && bias_tab && kcache && vcache && out && d_pos, "omp_debug_fused_self_attn: null pointer");
+  OMP_CHECK_ARG(R > 0 && Lmax > 0, "omp_debug_fused_self_attn: R and Lmax must be positive (R=%d Lmax=%d)", R, Lmax);
+  if (embed) {
+    OMP_CHECK_ARG(seq && word_emb && pos_tab && emb_g && emb_b && x_out && seq_ld > 0,
+                  "omp_debug_fused_self_attn: embed needs seq, seq_ld > 0, word_emb, pos_tab, emb_g, emb_b and x_out");
+  } else {
+    OMP_CHECK_ARG(x, "omp_debug_fused_self_attn: null pointer");
+  }
+  FusedSaP fp;
+  fp.x = x; fp.ln_g = ln_g; fp.ln_b = ln_b; fp.eps = eps;
+  fp.W = reinterpret_cast<const bf16_t*>(W); fp.bias_tab = bias_tab;
+  fp.kc = reinterpret_cast<bf16_t*>(kcache); fp.vc = reinterpret_cast<bf16_t*>(vcache);
+  fp.out = reinterpret_cast<bf16_t*>(out); fp.d_pos = d_pos; fp.R = R; fp.Lmax = Lmax;
+  fp.seq = seq; fp.seq_ld = seq_ld; fp.word = word_emb; fp.pos_tab = pos_tab; fp.emb_g = emb_g; fp.emb_b = emb_b;
+  fp.x_out = x_out;
+  return launch_fused_sa(fp, embed != 0, (hipStream_t)s);
 }
 
 extern "C" int omp_debug_cross_nt(int on) {

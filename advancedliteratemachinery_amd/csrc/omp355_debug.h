@@ -49,6 +49,16 @@ int omp_debug_set_gemm_trace(void* buffer, int64_t n_workgroups);
 int omp_debug_swin_attn_impl(int which); /* 0 = matrix-core kernel (default), 1 = scalar cross-check kernel, 2 = matrix cores with per-score table lookups */
 int omp_debug_dec_fused(int mode);       /* 0 = fused few-row decoder step kernels where they apply (default), 1 = one launch per op everywhere (A/B, cross-check) */
 int omp_debug_self_attn_impl(int which); /* 0 auto, 1 = one wave per (row, head), 2 = one wave per row (all 8 heads) */
+/* The fused few-row self-attention step of the point decoder on its own (csrc/decoder.hip dec_fused_self_attn_kernel, d = 512, 8 heads, bf16),
+ * through the engine's launch function: LayerNorm(x [R, 512] fp32) -> q | k | v = W [1536, 512] bf16 + bias_tab [Pmax, 1536] row *d_pos ->
+ * caches [R, Lmax, 512] bf16 appended at *d_pos -> out [R, 512] bf16.  embed != 0: layer 0 -- x is not read, the rows are
+ * LayerNorm_emb(word_emb[seq[r * seq_ld + *d_pos]] + pos_tab[*d_pos]) and are written to x_out [R, 512] fp32.  *d_pos < Lmax is the caller's
+ * duty (it lives in device memory).  OMP_ERR_INVALID: a null pointer (x with embed == 0; seq, word_emb, pos_tab, emb_g, emb_b, x_out with
+ * embed != 0), seq_ld <= 0 with embed, R <= 0, Lmax <= 0 */
+int omp_debug_fused_self_attn(const float* x, const float* ln_g, const float* ln_b, float eps, const void* W, const float* bias_tab,
+                              void* kcache, void* vcache, void* out, const int32_t* d_pos, int R, int Lmax, const int32_t* seq, int seq_ld,
+                              const float* word_emb, const float* pos_tab, const float* emb_g, const float* emb_b, float* x_out, int embed,
+                              omp_stream_t s);
 /* kernel of omp_head_softmax_mask_argmax (omp_decoder_run keeps its own choice): 0 = auto (default: a wave per row, the row in registers beyond
  * OMP355_SAMPLE_BLOCK_MAX_ROWS rows when ld % 4 == 0, the rows are 16-byte aligned and vocab <= 2048), 1 = a wave per row, 2 = the row in
  * registers (OMP_ERR_UNSUPPORTED when those preconditions fail), 3 = a workgroup per row; with 3 and advance != 0 d_pos points to two int32

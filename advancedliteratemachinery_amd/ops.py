@@ -530,6 +530,23 @@ def dec_fused(mode):
     _lib.check(_lib.lib().omp_debug_dec_fused(int(mode)), 'omp_debug_dec_fused')
 
 
+def self_attn_impl(which):
+    """debug/testing: kernel of dec_self_attn_step: 0 = by row count (default), 1 = one wave per (row, head), 2 = one wave per row."""
+    _lib.check(_lib.lib().omp_debug_self_attn_impl(int(which)), 'omp_debug_self_attn_impl')
+
+
+def fused_self_attn(x, ln_g, ln_b, W, bias_tab, kcache, vcache, out, d_pos, eps=1e-5, embed=None):
+    """debug/testing: the fused few-row self-attention step of the point decoder on its own (omp_debug_fused_self_attn, d = 512, 8 heads).
+    x [R, 512] fp32 (None with embed), W [1536, 512] bf16, bias_tab [Pmax, 1536] fp32, caches [R, Lmax, 512] bf16, out [R, 512] bf16.
+    embed: None, or (seq int32 [R, >= pos + 1], word_emb, pos_tab, emb_g, emb_b, x_out [R, 512] fp32) -- layer 0."""
+    R, Lmax = out.shape[0], kcache.shape[1]
+    seq, word, pos_tab, emb_g, emb_b, x_out = embed if embed is not None else (None,) * 6
+    rc = _lib.lib().omp_debug_fused_self_attn(ptr(x), ptr(ln_g), ptr(ln_b), float(eps), ptr(W), ptr(bias_tab), ptr(kcache), ptr(vcache),
+                                              ptr(out), ptr(d_pos), R, Lmax, ptr(seq), seq.stride(0) if seq is not None else 0, ptr(word),
+                                              ptr(pos_tab), ptr(emb_g), ptr(emb_b), ptr(x_out), 0 if embed is None else 1, stream())
+    _lib.check(rc, 'omp_debug_fused_self_attn')
+
+
 def sample_impl(which):
     """debug/testing: kernel of head_sample (omp_head_softmax_mask_argmax): 0 = auto (default), 1 = wave per row, 2 = the row in registers
     (refused unless the row stride is a multiple of 4, the rows are 16-byte aligned and vocab <= 2048), 3 = workgroup per row; with 3 and

@@ -254,7 +254,9 @@ int omp_dec_embed_ln(const int32_t* seq, int seq_ld, const int32_t* d_pos, const
 
 /* Append this step's k,v (from qkv [R,3d]) to the caches [R,Lmax,d] at *d_pos and attend the new
  * query over positions 0..*d_pos (causal self-attention with KV cache; head_dim = d/nH = 64).
- * Replaces self_attn of transformer.py:412-414/:438-440 + generate_square_subsequent_mask. */
+ * Replaces self_attn of transformer.py:412-414/:438-440 + generate_square_subsequent_mask.
+ * OMP_ERR_INVALID, nothing written: a null pointer, R <= 0, Lmax <= 0, d != 64 nH, a dtype other than OMP_F32 / OMP_BF16.  *d_pos < Lmax
+ * is the caller's duty (the position lives in device memory). */
 int omp_dec_self_attn_step(const void* qkv, void* kcache, void* vcache, void* out,
                            const int32_t* d_pos, int dtype, int R, int nH, int d, int Lmax,
                            omp_stream_t s);
