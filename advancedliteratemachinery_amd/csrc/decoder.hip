@@ -1772,8 +1772,8 @@ int self_attn_rows_split(const omp_decoder_plan* P, const omp_dec_layer& L, void
   return OMP_OK;
 }
 
-// Many-row phases (plan->rows_fused): the Linear layers as row-owner chains (bf16 engine: csrc/dec_rows.hip; parity engine, plan->gemm_x3:
-// csrc/dec_rows_x3.hip -- three bf16 matrix-core products per Linear over split operands, fp32 self-attention, split-plane cross-attention) --
+// Many-row phases (plan->rows_fused): the Linear layers as row-owner chains (csrc/dec_rows.hip; parity engine, plan->gemm_x3: its split
+// operand format -- three bf16 matrix-core products per Linear over split operands, fp32 self-attention, split-plane cross-attention) --
 // embedding | q k v, then per layer self-attention, out-projection .. cross-attention query, cross-attention, out-projection .. FFN .. next
 // layer's q k v (the last layer: .. prediction head): 2 + 4 per layer launches instead of 11 per layer + 5.  Prefill positions run the head too
 // (its logits are not sampled): one kernel variant fewer.  The step is cut at its cross-attention kernels (RowsStep::embed / pre_cross / cross /

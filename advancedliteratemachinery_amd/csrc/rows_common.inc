@@ -1,5 +1,6 @@
-// Shared pieces of the row-owner chain kernels (csrc/dec_rows.hip: bf16 operands; csrc/dec_rows_x3.hip: split-bf16 operands of the parity
-// engine): the per-wave weight stream with its register ring of asm loads and hand-counted waits, the LDS-only barrier, row LayerNorm.
+// Shared pieces of the row-owner chain kernels (csrc/dec_rows.hip: the decoder / Swin chains over bf16 operands and over the split-bf16 operands
+// of the parity engine; csrc/kv_rows.hip: the memory projection): the per-wave weight stream with its register ring of asm loads and
+// hand-counted waits, the LDS-only barrier, row LayerNorm.
 // Included inside each file's anonymous namespace.
 constexpr int NW = 8;                  // waves per workgroup
 constexpr int D = 512;                 // d_model

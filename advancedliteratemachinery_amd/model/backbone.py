@@ -116,8 +116,8 @@ class Encoder(object):
                 st.down_g = st.down_b = st.down_w = None
             st.out_g, st.out_b = f32('%snorm%d.weight' % (bb, s)), f32('%snorm%d.bias' % (bb, s))
             # row-owner chains of a C = 512 stage: packed weight streams per block (its proj + MLP + the next block's qkv) and the first block's
-            # qkv; the bf16 engine packs its bf16 matrices (csrc/dec_rows.hip), the parity engine the fp32 masters as (hi, lo) fragment pairs
-            # (csrc/dec_rows_x3.hip)
+            # qkv; the bf16 engine packs its bf16 matrices (csrc/dec_rows.hip: Bf16Rows), the parity engine the fp32 masters as (hi, lo) fragment pairs
+            # (SplitRows)
             st.rows_qkv0 = None
             if ((dtype == torch.bfloat16 or self.x3) and st.C == 512 and all(tuple(sd['%slayers.%d.blocks.%d.mlp.fc1.weight' % (bb, s, i)].shape) == (2048, 512) for i in range(dep))
                     and getattr(args, 'fused_mlp', True) and getattr(args, 'fused_attn', True)):
@@ -170,7 +170,7 @@ class Encoder(object):
             C = st.C
             blks = st.blocks
             if st.rows_qkv0 is not None and x.shape[0] >= ROWS_BLOCK_MIN_TOKENS:
-                # stage 2 as row-owner chains over split operands (csrc/dec_rows_x3.hip): per block the split-product window attention on fp32
+                # stage 2 as row-owner chains over split operands (csrc/dec_rows.hip: SplitRows): per block the split-product window attention on fp32
                 # q | k | v, then ONE launch for proj, norm2, fc1 + GELU, fc2 and the next block's norm1 + qkv
                 qkv = ops.swin_rows_qkv(x, (blks[0].n1g, blks[0].n1b), blks[0].qkv_b, st.rows_qkv0[0], st.rows_qkv0[1], eps=LN_EPS, x3=True)
                 att = torch.empty((x.shape[0], 2 * C), dtype=torch.bfloat16, device=x.device)

@@ -178,7 +178,7 @@ def pack_rows_mid(sa_out_w, ca_q_w):
 
 def _rows_ffn_pieces(ca_out_w, ff1_w, ff2_w):
     x3 = _same_kind(ca_out_w, ff1_w, ff2_w)
-    chunk = 128 if x3 else 256      # hidden units per chunk (csrc/dec_rows_x3.hip: HC3; csrc/dec_rows.hip: HC)
+    chunk = 128 if x3 else 256      # hidden units per chunk (csrc/dec_rows.hip: SplitRows::HC, Bf16Rows::HC)
     Hd, C = ff1_w.shape
     if ff2_w.shape != (C, Hd) or Hd % chunk or C != 512:
         raise ValueError('pack_rows_ffn: unsupported shapes %s / %s' % (tuple(ff1_w.shape), tuple(ff2_w.shape)))

@@ -346,7 +346,7 @@ class Decoder(object):
         esz = 4 if self.dtype == torch.float32 else 2   # bytes per (key, dim): a split-plane pair is 2 x 2
         P.dtype, P.n_layers, P.d_model, P.n_heads, P.d_ff, P.vocab = ops.dt(self.dtype), self.L, d, self.nH, self.ff, self.V
         P.pre_norm = 1 if a.tfm_pre_norm else 0
-        # row-owner chains: the bf16 engine's (csrc/dec_rows.hip) or, on a gemm_x3 plan, the parity engine's (csrc/dec_rows_x3.hip).  A phase that
+        # row-owner chains (csrc/dec_rows.hip): in the bf16 engine's operand format or, on a gemm_x3 plan, the parity engine's split one.  A phase that
         # takes the chains is a gemm_x3 plan whatever its row count (the tiled x3 GEMMs want more than 64 rows, the chains any number: the parity
         # tests lower rows_min to put the fixtures' 1 .. 64-row phases on the benchmark's kernels)
         rows_ok = bool(a.tfm_pre_norm and ph.R >= self.rows_min and d == 512 and self.ff == 2048 and self.nH == 8 and self.V % 4 == 0)

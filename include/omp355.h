@@ -471,7 +471,7 @@ typedef struct {
   const float *h0_b, *h1_b, *h2_b; /* tail 1 */
   float* logits;
   int32_t vocab;
-  /* x3 = 1: the PARITY engine's chains (csrc/dec_rows_x3.hip): every product as three bf16 matrix-core products of split operands.  att is then
+  /* x3 = 1: the PARITY engine's chains (csrc/dec_rows.hip, SplitRows): every product as three bf16 matrix-core products of split operands.  att is then
    * split pairs bf16 [R, 1024] = [hi | lo] (omp_split_bf16 / the split-plane cross-attention), q / qkv are fp32 [R, 512] / [R, 1536], and
    * wstream carries per (k-step, feature tile) the fragment of w_hi then of w_lo (twice the fragments; model/packing.py, x3=True); a
    * workgroup owns 48 rows. */

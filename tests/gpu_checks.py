@@ -678,7 +678,7 @@ def check_dec_rows(x3=False, xcd_mask=0, results=None):
     """Row-owner chains of the decoders' many-row phases (csrc/dec_rows.hip, round 5) against a CPU restatement of the sub-layers they
     replace (transformer.py:430-454 forward_pre, :302-328 embeddings, block/mlp.py head) with bf16 rounding where the kernels round
     (LayerNorm outputs, attention outputs, hidden activations, q / k / v), fp32 elsewhere.  R = 200 rows: three workgroups of 80 rows,
-    the last one ragged (40 rows).  x3: the parity engine's chains (csrc/dec_rows_x3.hip: split operands, fp32 weights / outputs, 48 rows
+    the last one ragged (40 rows).  x3: the parity engine's chains (csrc/dec_rows.hip, SplitRows: split operands, fp32 weights / outputs, 48 rows
     per workgroup) against plain fp32 arithmetic.  xcd_mask: the launches confined to those XCDs (omp_dec_rows_args.xcd_mask); results: a list
     that receives the device outputs (check_dec_rows_xcd compares them bit for bit across masks)."""
     from advancedliteratemachinery_amd.model import packing
@@ -1016,7 +1016,7 @@ def check_decoder_x3(with_mask=True):
         if eng == 'bf16x3':
             ph = [p_ for p_ in dec._phases.values() if p_.R == R]
             out.append(rrec('decoder_x3: the %d-row phases run gemm_x3 plans' % R, 0 if ph and all(p_.plan.gemm_x3 == 1 for p_ in ph) else 1, 0))
-            # round 5: the same phases as row-owner chains over split operands (csrc/dec_rows_x3.hip; 103 rows: three workgroups of 48, the last ragged)
+            # round 5: the same phases as row-owner chains over split operands (csrc/dec_rows.hip, SplitRows; 103 rows: three workgroups of 48, the last ragged)
             keep = dec.rows_min
             try:
                 dec.rows_min = 1

@@ -1,4 +1,4 @@
-"""Row-owner chains at every row count the engine launches (csrc/dec_rows.hip, csrc/dec_rows_x3.hip, csrc/kv_rows.hip).
+"""Row-owner chains at every row count the engine launches (csrc/dec_rows.hip for both engines, csrc/kv_rows.hip).
 
 The chains are row-local: output row r depends on input row r and on the weights only.  So every chain is checked in two steps:
   * a BASE launch of 256 distinct rows (ordinary random rows and rows at the LayerNorm's and the arithmetic's edges) against a float64

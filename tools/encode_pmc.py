@@ -113,7 +113,7 @@ def read(path, ctr):
                 c = 'kv'
             elif 'mlp_fused_kernel' in k:
                 c = 'mlp'
-            elif 'dec_rows_ffn_kernel' in k or 'dec_rows_x3_ffn_kernel' in k:
+            elif 'dec_rows_ffn_kernel' in k:
                 c = 'chain'
             elif 'gemm_256' in k or 'gemm_4w' in k or ('gemm_dma' in k and ('Li128ELi128E' in k or '128, 128' in k)):
                 c = 'gemm'
