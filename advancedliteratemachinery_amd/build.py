@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libomp355.so')
 SOURCES = ['api.hip', 'gemm.hip', 'mlp.hip', 'norm.hip', 'swin_attn.hip', 'swin_block.hip', 'fpn.hip', 'decoder.hip', 'dec_rows.hip', 'kv_rows.hip', 'vit.hip', 'preprocess.hip', 'word_crop.hip', 'lexicon.hip', 'window_points.hip', 'overlap.hip', 'reading.hip']
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm256.inc'), os.path.join(CSRC, 'gemm4w.inc'), os.path.join(CSRC, 'gemm4wr.inc'), os.path.join(CSRC, 'gemm4wp.inc'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm256.inc'), os.path.join(CSRC, 'gemm4w.inc'), os.path.join(CSRC, 'gemm4wr.inc'), os.path.join(CSRC, 'gemm4wp.inc'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(CSRC, 'swin_common.h'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
 AUDITED = ('gemm.hip', 'dec_rows.hip', 'kv_rows.hip')   # their device assembly stays next to the object: the audits read it
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 

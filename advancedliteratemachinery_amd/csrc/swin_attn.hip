@@ -15,10 +15,9 @@
 // needs no cross-lane traffic; K and V of the window/head are staged once in LDS (fp32) and read
 // as wave-wide broadcasts (conflict-free ds_read_b128).
 #include "common.h"
+#include "swin_common.h"
 
 namespace {
-
-constexpr int WS = 7, WT = 49, HD = 32;
 
 template <typename T>
 __global__ __launch_bounds__(256) void swin_attn_kernel(const T* __restrict__ qkv,
@@ -99,9 +98,7 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(const T* __restrict__ qk
 
   int rid_i = 0;
   if (shift > 0) {
-    const int ry = sy < Hp - WS ? 0 : (sy < Hp - shift ? 1 : 2);
-    const int rx = sx < Wp - WS ? 0 : (sx < Wp - shift ? 1 : 2);
-    rid_i = ry * 3 + rx;
+    rid_i = swin_region(sy, sx, Hp, Wp, shift);
   }
 
   float sc[WT];
@@ -121,9 +118,7 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(const T* __restrict__ qk
     a += tab[wave][(ty - jy + WS - 1) * (2 * WS - 1) + (tx - jx + WS - 1)];
     if (shift > 0) {
       const int ssy = wy * WS + jy, ssx = wx * WS + jx;
-      const int ry = ssy < Hp - WS ? 0 : (ssy < Hp - shift ? 1 : 2);
-      const int rx = ssx < Wp - WS ? 0 : (ssx < Wp - shift ? 1 : 2);
-      if (ry * 3 + rx != rid_i) a += -100.0f;
+      if (swin_region(ssy, ssx, Hp, Wp, shift) != rid_i) a += -100.0f;
     }
     sc[j] = a;
     mx = fmaxf(mx, a);
@@ -327,9 +322,7 @@ __global__ __launch_bounds__(256, 2) void swin_attn_mfma_kernel(const T* __restr
       if (px >= Wp) px -= Wp;
       my_tok = (py < H && px < W) ? (b * H + py) * W + px : -1;   // token rows fit 32 bits (checked by the launcher)
       if (w.masked) {
-        const int ry = sy < Hp - WS ? 0 : (sy < Hp - shift ? 1 : 2);
-        const int rx = sx < Wp - WS ? 0 : (sx < Wp - shift ? 1 : 2);
-        w.my_rid = ry * 3 + rx;
+        w.my_rid = swin_region(sy, sx, Hp, Wp, shift);
       }
     }
     auto load_chunk = [&](int tok, int sel, int d0) -> frag {   // 16 bytes of q (sel 0) / k (1) / v (2) of token tok at head dims [d0, d0 + NV)
@@ -591,9 +584,7 @@ __global__ __launch_bounds__(256, 2) void swin_attn_x3_kernel(const float* __res
       if (px >= Wp) px -= Wp;
       my_tok = (py < H && px < W) ? (b * H + py) * W + px : -1;
       if (edge) {
-        const int ry = sy < Hp - WS ? 0 : (sy < Hp - shift ? 1 : 2);
-        const int rx = sx < Wp - WS ? 0 : (sx < Wp - shift ? 1 : 2);
-        my_rid = ry * 3 + rx;
+        my_rid = swin_region(sy, sx, Hp, Wp, shift);
       }
     }
     const int sy_hi = wy * WS + WS - 1 + shift, sx_hi = wx * WS + WS - 1 + shift;

@@ -65,7 +65,7 @@ def pack_mlp(fc1_w, fc1_b, fc2_w):
 
 def pack_attn_block(qkv_w, proj_w, n_heads):
     """Fragment-major weight image for the fused attention half of a Swin block whose weights do not fit in LDS
-    (csrc/swin_block.hip::swin_block256_kernel, C = 256 with 8 heads).  qkv_w [3C, C], proj_w [C, C] in bf16 ->
+    (csrc/swin_block.hip::swin_block_kernel<Stage1>, C = 256 with 8 heads).  qkv_w [3C, C], proj_w [C, C] in bf16 ->
     bf16 [3C*C + C*C], two regions:
 
       qkv : fragment ((h * KS + ks) * 6 + sel * 2 + dt) of 64 lanes x 8 elements; lane = 16 g + li holds

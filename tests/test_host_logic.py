@@ -428,52 +428,58 @@ def test_split_bf16_products_are_one_gemm_over_3k():
     assert float((y1 - ref).abs().max() / ref.abs().max()) > 2.0 ** -10
 
 
-def test_swin_block_tile_layout_identities():
-    """csrc/swin_block.hip addresses its bf16 tiles ([rows][128] at 256 B per row, 16-byte chunk c of row r at slot c ^ (r & 15))
-    through three shortcuts; each is an identity over the index ranges the kernel uses."""
-    def sw_off(row, chunk):
-        return row * 256 + ((chunk ^ (row & 15)) << 4)
+@pytest.mark.parametrize('C', [128, 256])
+def test_swin_block_tile_layout_identities(C):
+    """csrc/swin_block.hip (swin_block_kernel<Stage0 / Stage1>: C = 128 with 4 heads, C = 256 with 8) addresses its bf16 tiles ([rows][C]
+    at PITCH = 2 C bytes per row, 16-byte chunk c of row r at slot c ^ (r & 15); at C = 128 also the resident weight image) through
+    shortcuts that fold the k-step / piece index in by XOR; each is an identity over the index ranges the kernel uses.  LayerNorm
+    spreads a token over L = C / 16 lanes: 8 at pitch 256, 16 at pitch 512."""
+    PITCH, L, heads = 2 * C, C // 16, C // 32
 
-    # (1) fragment reads: rows R + li with R a multiple of 16 -> R * 256 + cx[ks], cx[ks] = li * 256 + (((ks * 4 + g) ^ li) << 4);
-    #     the 16 lanes of one k-group hit 16 different chunk slots (conflict-free ds_read_b128)
-    for R in (0, 16, 48, 128, 256 + 96):
-        for ks in range(4):
+    def sw_off(row, chunk):
+        return row * PITCH + ((chunk ^ (row & 15)) << 4)
+
+    # (1) fragment reads: rows R + li with R a multiple of 16, k-step ks -> R * PITCH + cx[ks], cx[ks] = li * PITCH + (((ks * 4 + g) ^ li) << 4)
+    #     (Stage0 keeps the cx[ks]); the same offset as cx0 ^ (ks << 6), cx0 = li * PITCH + ((g ^ li) << 4) (Stage1, rolled k loop); the 16
+    #     lanes of one k-group hit 16 different chunk slots (conflict-free ds_read_b128)
+    for R in (0, 16, 32, 48, 128, 256 + 96):
+        for ks in range(C // 32):
             for g in range(4):
                 slots = set()
                 for li in range(16):
-                    cx = li * 256 + (((ks * 4 + g) ^ li) << 4)
-                    assert R * 256 + cx == sw_off(R + li, ks * 4 + g)
+                    cx = li * PITCH + (((ks * 4 + g) ^ li) << 4)
+                    cx0 = li * PITCH + ((g ^ li) << 4)
+                    assert R * PITCH + cx == sw_off(R + li, ks * 4 + g)
+                    assert cx0 ^ (ks << 6) == cx
                     slots.add((cx >> 4) & 15)
                 assert len(slots) == 16
-    # (2) LayerNorm writes: wave `head`, lane (tk, lj), pass `it`, piece k -> token row it * 32 + head * 8 + tk, fp32 piece c = k * 8 + lj,
-    #     i.e. bf16 chunk c >> 1 = k * 4 + (lj >> 1), half (lj & 1); the kernel keeps ONE offset and folds k in as ^ (k << 6)
-    for head in range(4):
-        for tk in range(8):
-            for lj in range(8):
-                ln_row = head * 8 + tk
-                ln_off = ln_row * 256 + (((lj >> 1) ^ (ln_row & 15)) << 4) + (lj & 1) * 8
-                for it in range(2):
-                    for k in range(4):
-                        row, c = it * 32 + ln_row, k * 8 + lj
-                        assert it * 32 * 256 + (ln_off ^ (k << 6)) == sw_off(row, c >> 1) + (c & 1) * 8
-    # every (row, 8-byte half chunk) of the 64 x 128 tile is written exactly once per window
+    # (2) LayerNorm writes: wave `head`, lane (tk, lj), pass `it`, piece k -> token row it * 32 + head * (64 / L) + tk, fp32 piece
+    #     c = k * L + lj, i.e. bf16 chunk c >> 1, half c & 1 = lj & 1; the kernel keeps ONE offset and folds k in as ^ (k * L * 8), which is
+    #     ^ (k << 6) at C = 128 and ^ (k << 7) at C = 256; every (row, 8-byte half chunk) of the 64 x C tile is written exactly once per window
+    assert L * 8 == (1 << 6 if C == 128 else 1 << 7)
     seen = set()
-    for head in range(4):
+    for head in range(heads):
         for lane in range(64):
-            tk, lj = lane >> 3, lane & 7
+            tk, lj = lane // L, lane % L
+            assert (tk, lj) == ((lane >> 3, lane & 7) if C == 128 else (lane >> 4, lane & 15))
+            ln_row = head * (64 // L) + tk
+            ln_off = ln_row * PITCH + (((lj >> 1) ^ (ln_row & 15)) << 4) + (lj & 1) * 8
             for it in range(2):
                 for k in range(4):
-                    seen.add((it * 32 + head * 8 + tk, k * 8 + lj))
-    assert len(seen) == 64 * 32
+                    row, c = it * 32 + ln_row, k * L + lj
+                    assert it * 32 * PITCH + (ln_off ^ (k * L * 8)) == sw_off(row, c >> 1) + (c & 1) * 8
+                    seen.add((row, c))
+    assert len(seen) == 64 * (C // 4)
+    assert {r for r, _ in seen} == set(range(64))
     # (3) O^T accumulator pieces: head h, dim tile dt, lane (li, g) holds dims dt * 16 + 4 g .. + 4 of query t4 * 16 + li
-    for h in range(4):
+    for h in range(heads):
         for li in range(16):
             for g in range(4):
-                off = [li * 256 + (((h * 4 + dt * 2 + (g >> 1)) ^ li) << 4) + (g & 1) * 8 for dt in range(2)]
+                off = [li * PITCH + (((h * 4 + dt * 2 + (g >> 1)) ^ li) << 4) + (g & 1) * 8 for dt in range(2)]
                 for t4 in range(4):
                     for dt in range(2):
                         q, ch = t4 * 16 + li, h * 32 + dt * 16 + 4 * g      # channel of the first of the 4 values
-                        assert t4 * 4096 + off[dt] == sw_off(q, ch >> 3) + ((ch >> 2) & 1) * 8
+                        assert t4 * 16 * PITCH + off[dt] == sw_off(q, ch >> 3) + ((ch >> 2) & 1) * 8
     # (4) window-local token t -> (t // 7, t % 7) as (t * 37) >> 8 for every t the kernel decodes
     for t in range(64):
         assert (t * 37) >> 8 == t // 7
@@ -544,39 +550,6 @@ def test_pack_attn_block_fragment_order():
         for lane in (0, 9, 33, 63):
             g, li = lane >> 4, lane & 15
             assert torch.equal(frag[lane], proj[32 * w + 16 * nt + li, 32 * ks + 8 * g:32 * ks + 8 * g + 8])
-
-
-def test_swin_block256_tile_layout_identities():
-    """The C = 256 variant (rows of 512 B = 32 chunks, slot = chunk ^ (row & 15)) folds the k-step / piece index into its offsets by XOR."""
-    def sw_off(row, chunk):
-        return row * 512 + ((chunk ^ (row & 15)) << 4)
-
-    for li in range(16):
-        for g in range(4):
-            cx0 = li * 512 + ((g ^ li) << 4)
-            for ks in range(8):
-                for R in (0, 16, 32, 48):
-                    assert R * 512 + (cx0 ^ (ks << 6)) == sw_off(R + li, ks * 4 + g)
-    seen = set()
-    for head in range(8):
-        for lane in range(64):
-            tk, lj = lane >> 4, lane & 15
-            ln_row = head * 4 + tk
-            ln_off = ln_row * 512 + (((lj >> 1) ^ (ln_row & 15)) << 4) + (lj & 1) * 8
-            for it in range(2):
-                for k in range(4):
-                    row, c = it * 32 + ln_row, k * 16 + lj            # fp32 piece c of the 1 KB row -> bf16 chunk c >> 1, half c & 1
-                    assert it * 32 * 512 + (ln_off ^ (k << 7)) == sw_off(row, c >> 1) + (c & 1) * 8
-                    seen.add((row, c))
-    assert len(seen) == 64 * 64
-    for h in range(8):
-        for li in range(16):
-            for g in range(4):
-                off = [li * 512 + (((h * 4 + dt * 2 + (g >> 1)) ^ li) << 4) + (g & 1) * 8 for dt in range(2)]
-                for t4 in range(4):
-                    for dt in range(2):
-                        q, ch = t4 * 16 + li, h * 32 + dt * 16 + 4 * g
-                        assert t4 * 8192 + off[dt] == sw_off(q, ch >> 3) + ((ch >> 2) & 1) * 8
 
 
 def test_split_plane_slab_indexing_is_a_bijection():
