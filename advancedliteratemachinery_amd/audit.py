@@ -1,9 +1,10 @@
-"""Build audit of gemm_4w (csrc/gemm4w.inc): the kernel addresses all 256 accumulator registers literally from asm statements, so the
-compiler must neither spill nor touch the accumulator file itself (cdna_hip_programming.md 5.7 item 4).  Reads the device assembly hipcc
-leaves next to the object (advancedliteratemachinery_amd/build.py compiles gemm.hip with -save-temps=obj) and demands, for EVERY gemm_4w
-instantiation: no scratch, no spill, and no v_accvgpr_* / scratch_* instruction outside an ;;#ASMSTART ... ;;#ASMEND block; for gemm_4w_r /
+"""Build audit of the gemm_4w kernels (csrc/gemm4w.hip, gemm4wr.hip, gemm4wp.hip): they address all 256 accumulator registers literally from asm
+statements, so the compiler must neither spill nor touch the accumulator file itself (cdna_hip_programming.md 5.7 item 4).  Reads the device
+assembly hipcc leaves next to the object (advancedliteratemachinery_amd/build.py compiles those units with -save-temps=obj) and demands, for EVERY
+gemm_4w instantiation: no scratch, no spill, and no v_accvgpr_* / scratch_* instruction outside an ;;#ASMSTART ... ;;#ASMEND block; for gemm_4w_r /
 gemm_4w_p (asm fragment loads, hand-counted waits) also no register copy inside the stage loop.
-    python -m advancedliteratemachinery_amd.audit [path/to/gemm-hip-amdgcn-amd-amdhsa-gfx950.s]   -> exit status 1 on a violation
+    python -m advancedliteratemachinery_amd.audit [path/to/UNIT-hip-amdgcn-amd-amdhsa-gfx950.s ...]   -> exit status 1 on a violation
+(without a path: every audited unit of build.py whose assembly is on disk)
 Part of the package (round 5; it lived under tools/): build.py runs it on the assembly BEFORE it links, so a library whose asm-addressed
 kernels the compiler broke is never left on disk."""
 import os
@@ -11,13 +12,16 @@ import re
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEFAULT = os.path.join(HERE, 'csrc', 'build', 'gemm-hip-amdgcn-amd-amdhsa-gfx950.s')
+# a production instantiation of gemm_4w_r / gemm_4w_p by its mangled name: ABL = 0 (then X3, if any) closes the template arguments, the parameter
+# block is the one argument.  Everything else is an ablation / trace instantiation.  A kernel that does not match is skipped, so audit() counts
+# what it checked and audit_unit() refuses a unit of such kernels with none checked.
+PRODUCTION = r'ELi0E(Lb[01]E)?EEvN\S*5GemmPE$'
 
 
-def audit(path=DEFAULT):
-    """-> (number of gemm_4w kernels seen, list of violation strings)"""
+def audit(path):
+    """-> (number of gemm_4w kernels seen, list of violation strings, number of gemm_4w_r / _p kernels that went through the stage-loop check)"""
     text = open(path).read()
-    bad, seen = [], 0
+    bad, seen, checked = [], 0, 0
     # kernel bodies: from the label to s_endpgm
     for m in re.finditer(r'^(_ZN\S*gemm_4w\S*):[^\n]*\n(.*?)\ts_endpgm', text, re.S | re.M):
         name, body = m.group(1), m.group(2)
@@ -36,8 +40,9 @@ def audit(path=DEFAULT):
     # rematerialisation) could read it before the data arrives.  Demand that the innermost loop (the stages) holds no v_mov at all.
     for m in re.finditer(r'^(_ZN\S*gemm_4w_[rp]\S*):[^\n]*\n(.*?)\ts_endpgm', text, re.S | re.M):
         name, lines = m.group(1), m.group(2).split('\n')
-        if not re.search(r'ELi0E(Lb[01]E)?EEvNS', name):
+        if not re.search(PRODUCTION, name):
             continue   # ablation / trace instantiations (wrong results by construction or development only)
+        checked += 1
         # innermost loops: the header block carries "Inner Loop Header", its other blocks "in Loop: Header=BBx_y Depth=d" (LLVM's comments)
         inner = set()
         for i, ln in enumerate(lines):
@@ -74,7 +79,7 @@ def audit(path=DEFAULT):
         a = re.search(r'\.agpr_count:\s+(\d+)', meta)
         if a and int(a.group(1)) != 256:
             bad.append('%s: .agpr_count = %s (the kernel names a0..a255)' % (name, a.group(1)))
-    return seen, bad
+    return seen, bad, checked
 
 
 def _regs(text):
@@ -149,10 +154,30 @@ def audit_dec_rows(path):
     return seen, bad
 
 
+def audit_unit(path):
+    """The audit of one unit's device assembly, chosen by the kernels the unit holds: gemm_4w* kernels -> audit(), refusing a unit of
+    gemm_4w_r / gemm_4w_p kernels of which the stage-loop check recognised none; the row-owner kernels -> audit_dec_rows().
+    -> (number of audited kernels seen, list of violation strings, number of stage-loop checks)"""
+    text = open(path).read()
+    if not re.search(r'^_ZN\S*gemm_4w\S*:', text, re.M):
+        return audit_dec_rows(path) + (0,)
+    seen, bad, checked = audit(path)
+    if checked == 0 and re.search(r'^_ZN\S*gemm_4w_[rp]\S*:', text, re.M):
+        bad.append('%s: gemm_4w_r / gemm_4w_p kernels, none of them recognised as a production instantiation: the stage loop went unchecked' % os.path.basename(path))
+    return seen, bad, checked
+
+
 if __name__ == '__main__':
-    path = sys.argv[1] if len(sys.argv) > 1 else DEFAULT
-    n, bad = audit_dec_rows(path) if 'dec_rows' in os.path.basename(path) else audit(path)
-    print('register audit of %s: %d kernels, %d violations' % (os.path.basename(path), n, len(bad)))
-    for b in bad:
-        print('  ' + b)
-    sys.exit(1 if bad or n == 0 else 0)
+    paths = sys.argv[1:]
+    if not paths:
+        from . import build
+        paths = [p for p in map(build._asm_of, build.AUDITED) if os.path.exists(p)]
+    status = 0 if paths else 1
+    for path in paths:
+        n, bad, checked = audit_unit(path)
+        print('register audit of %s: %d kernels, %d through the stage-loop check, %d violations' % (os.path.basename(path), n, checked, len(bad)))
+        for b in bad:
+            print('  ' + b)
+        if bad or n == 0:
+            status = 1
+    sys.exit(status)

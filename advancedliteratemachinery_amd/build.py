@@ -15,9 +15,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libomp355.so')
-SOURCES = ['api.hip', 'gemm.hip', 'mlp.hip', 'norm.hip', 'swin_attn.hip', 'swin_block.hip', 'fpn.hip', 'decoder.hip', 'dec_rows.hip', 'kv_rows.hip', 'vit.hip', 'preprocess.hip', 'word_crop.hip', 'lexicon.hip', 'window_points.hip', 'overlap.hip', 'reading.hip']
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm256.inc'), os.path.join(CSRC, 'gemm4w.inc'), os.path.join(CSRC, 'gemm4wr.inc'), os.path.join(CSRC, 'gemm4wp.inc'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(CSRC, 'swin_common.h'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
-AUDITED = ('gemm.hip', 'dec_rows.hip', 'kv_rows.hip')   # their device assembly stays next to the object: the audits read it
+SOURCES = ['api.hip', 'gemm.hip', 'gemm256.hip', 'gemm4w.hip', 'gemm4wr.hip', 'gemm4wp.hip', 'mlp.hip', 'norm.hip', 'swin_attn.hip', 'swin_block.hip', 'fpn.hip', 'decoder.hip', 'dec_rows.hip', 'kv_rows.hip', 'vit.hip', 'preprocess.hip', 'word_crop.hip', 'lexicon.hip', 'window_points.hip', 'overlap.hip', 'reading.hip']
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(CSRC, 'swin_common.h'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
+# the units that hold gemm_4w* kernels and the row-owner kernels: their device assembly stays next to the object, the audits read it
+AUDITED = ('gemm4w.hip', 'gemm4wr.hip', 'gemm4wp.hip', 'dec_rows.hip', 'kv_rows.hip')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 
@@ -94,7 +95,7 @@ def build(force=False, verbose=True):
         return r
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), int(os.environ.get('MAX_JOBS', 16)))) as ex:
             list(ex.map(run, jobs))
     # the register audits read the device assembly of THIS build and run before the link: a library whose asm-addressed kernels the
     # compiler broke (spills, accumulator-file traffic, copies of registers with loads in flight) must not be left on disk
@@ -113,7 +114,7 @@ def build(force=False, verbose=True):
 
 
 def _audit(audited):
-    """gemm_4w names all 256 accumulator registers in asm; gemm_4w_r / _p and the decoders' row-owner kernel (csrc/dec_rows.hip) load
+    """gemm_4w (csrc/gemm4w.hip, gemm4wr.hip, gemm4wp.hip) names all 256 accumulator registers in asm; gemm_4w_r / _p and the decoders' row-owner kernel (csrc/dec_rows.hip) load
     operand fragments with asm statements and count the waits by hand: refuse a build in which the compiler spilled, used the
     accumulator file itself or copied a register with a load in flight (advancedliteratemachinery_amd/audit.py; silent corruption otherwise)."""
     from . import audit
@@ -124,7 +125,7 @@ def _audit(audited):
             continue   # the assembly of exactly this object passed before
         if not os.path.exists(asm):   # build() recompiles an audited source with neither stamp nor assembly: cannot happen
             raise RuntimeError('%s register audit: %s is missing' % (stem, asm))
-        n, bad = audit.audit(asm) if src == 'gemm.hip' else audit.audit_dec_rows(asm)
+        n, bad, _ = audit.audit_unit(asm)   # by what the unit holds; a unit of gemm_4w_r / _p kernels with no stage loop checked is a violation
         if bad or n == 0:
             raise RuntimeError('%s register audit failed (%d kernels):\n%s' % (stem, n, '\n'.join(bad) or 'no audited kernel found in ' + asm))
         with open(astamp, 'w') as f:

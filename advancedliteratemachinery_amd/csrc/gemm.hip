@@ -15,206 +15,10 @@
 // rows of W) and j = token m (B operand = rows of A).  A lane then owns 4 CONSECUTIVE output
 // features of one token (acc[r] <-> n = 4*(lane>>4)+r, m = lane&15), so bias loads and C stores
 // are 8/16-byte vectors instead of 4 scalar stores.
-#include <type_traits>
+#include "gemm_common.h"
 
-#include "common.h"
-
+namespace omp_gemm {
 namespace {
-
-
-struct GemmP {
-  const void* A; int64_t lda;
-  const void* W; int64_t ldw;
-  const float* bias; const int32_t* bias_row; int64_t bias_row_stride;
-  const void* residual; int64_t ldr;
-  void* C; int64_t ldc;
-  int64_t M; int N; int K;
-  int act; int trans_out; int64_t trans_rows, trans_ld;
-  int tiles_m, tiles_n; int small_hint;
-  const float* ln_g; const float* ln_b; float ln_eps;   // optional LayerNorm prologue (A is fp32)
-  int store_mode; int bias_m;                           // OMP_STORE_*; bias indexed by m instead of n
-  int kv_B, kv_tok, kv_mpad, kv_nH, kv_kb;              // blocked K / V^T destination geometry
-  void* C2; int64_t ldc2;                               // optional second destination without the residual
-  int a_wrap;                                           // > 0: A rows are split-bf16 pairs [hi | lo] of a_wrap elements, K columns beyond wrap back (bf16x3)
-  int split_out;                                        // bf16 destination written as split pairs: hi at column n, lo at column N + n
-  unsigned long long* trace;                            // debug: per-workgroup phase timestamps (gemm_dma<..., TRACE>)
-};
-
-// bf16 destinations take the bf16 engine's GELU everywhere (vectorised or not: a value must not depend on which
-// kernel or epilogue path produced it), fp32 destinations the < 1 ulp erf form
-template <typename TOut>
-__device__ __forceinline__ float apply_act(float v, int act, bool precise = false) {
-  if (act == OMP_ACT_GELU) {
-    if constexpr (std::is_same<TOut, bf16_t>::value) return precise ? gelu_erf(v) : gelu_fast2(f32x2{v, 0.0f})[0];
-    else return gelu_erf(v);
-  }
-  if (act == OMP_ACT_RELU) return fmaxf(v, 0.0f);
-  return v;
-}
-
-// Store 4 consecutive-n values v (bias and activation already applied) of token m: adds the residual and
-// honours the destination layout (plain / transposed / blocked K / blocked V^T).
-template <typename TOut>
-__device__ __forceinline__ void store4(const GemmP& p, int64_t m, int n, const float* vin) {
-  if (m >= p.M || n >= p.N) return;
-  const TOut* res = reinterpret_cast<const TOut*>(p.residual);
-  TOut* C = reinterpret_cast<TOut*>(p.C);
-  float v[4] = {vin[0], vin[1], vin[2], vin[3]};
-  if (p.store_mode == OMP_STORE_KBLK) {
-    // m = memory token (image b, key ml), n..n+3 = 4 dims of one head of one (decoder, layer) slab:
-    // K slab [nl][b][h][Mpad][64]
-    const int d = p.kv_nH * 64;
-    const int b = (int)(m / p.kv_tok), ml = (int)(m % p.kv_tok);
-    const int nl = n / d, h = (n % d) >> 6, dd = n & 63;
-    if constexpr (sizeof(TOut) == 2) {
-      if (p.split_out) {   // split planes: block ml / 32 = [hi plane 32 x 64 | lo plane]
-        TOut* dst = C + (((((int64_t)nl * p.kv_B + b) * p.kv_nH + h) * (p.kv_mpad >> 5) + (ml >> 5)) * 2) * 2048 + (ml & 31) * 64 + dd;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (n + r < p.N) {
-            const bf16_t hi = (bf16_t)v[r];
-            dst[r] = hi;
-            dst[2048 + r] = (bf16_t)(v[r] - (float)hi);
-          }
-        return;
-      }
-    }
-    TOut* dst = C + ((((int64_t)nl * p.kv_B + b) * p.kv_nH + h) * p.kv_mpad + ml) * 64 + dd;
-    if (n + 3 < p.N) {
-      if constexpr (sizeof(TOut) == 4) *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
-      else *reinterpret_cast<bf16x4*>(dst) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < p.N) dst[r] = from_f32<TOut>(v[r]);
-    }
-    return;
-  }
-  if (p.store_mode == OMP_STORE_VBLK) {
-    // swapped operands: m = value feature (decoder-layer nl, head h, dim dd), n..n+3 = 4 memory tokens.
-    // V^T slab [nl][b][h][Mpad/KB][64][KB]; inside a block the KB keys sit in the order the PV matrix-core
-    // product consumes them (bf16: slot 8g + 4*half + r <-> key 16*half + 4g + r; f32: natural order).
-    const int d = p.kv_nH * 64, KB = p.kv_kb;
-    const int nl = (int)(m / d), h = (int)(m % d) >> 6, dd = (int)m & 63;
-    const int PLN = (sizeof(TOut) == 2 && p.split_out) ? 2 : 1;   // split planes: a block is [hi plane 64 x KB | lo plane]
-    auto slot = [&](int tok, int& b) -> int64_t {
-      b = tok / p.kv_tok;
-      const int ml = tok - b * p.kv_tok;
-      const int blk = ml / KB, kl = ml - blk * KB;
-      const int pos = (KB == 32) ? (((kl & 15) >> 2) * 8 + (kl >> 4) * 4 + (kl & 3)) : kl;
-      return ((((int64_t)nl * p.kv_B + b) * p.kv_nH + h) * (p.kv_mpad / KB) + blk) * (64 * KB * PLN) + dd * KB + pos;
-    };
-    // element by element (split planes; tokens per image not a multiple of 4: MGP-STR's 257): ONE division for the 4 tokens -- (image, key) of the
-    // first, then walked -- instead of three per element (round 6: the V^T projection of a ViT block spent 540 us here against 200 for the product)
-    auto walk = [&](auto&& put) {
-      int b = n / p.kv_tok, ml = n - b * p.kv_tok;
-      const int64_t per_head = (int64_t)(p.kv_mpad / KB) * (64 * KB * PLN);
-      int64_t base = (((int64_t)nl * p.kv_B + b) * p.kv_nH + h) * per_head + dd * KB;
-      const int sh = KB == 32 ? 5 : 4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (n + r < p.N) {
-          const int blk = ml >> sh, kl = ml & (KB - 1);
-          const int pos = (KB == 32) ? (((kl & 15) >> 2) * 8 + (kl >> 4) * 4 + (kl & 3)) : kl;
-          put(base + (int64_t)blk * (64 * KB * PLN) + pos, r);
-        }
-        if (++ml == p.kv_tok) { ml = 0; base += (int64_t)p.kv_nH * per_head; }
-      }
-    };
-    if constexpr (sizeof(TOut) == 2) {
-      if (p.split_out) {
-        walk([&](int64_t i, int r) {
-          const bf16_t hi = (bf16_t)v[r];
-          C[i] = hi;
-          C[i + 64 * KB] = (bf16_t)(v[r] - (float)hi);
-        });
-        return;
-      }
-    }
-    if (n + 3 < p.N && (p.kv_tok & 3) == 0) {   // 4 tokens of one image, contiguous slots
-      int b0;
-      const int64_t i0 = slot(n, b0);
-      if constexpr (sizeof(TOut) == 4) *reinterpret_cast<f32x4*>(C + i0) = f32x4{v[0], v[1], v[2], v[3]};
-      else *reinterpret_cast<bf16x4*>(C + i0) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    } else {
-      walk([&](int64_t i, int r) { C[i] = from_f32<TOut>(v[r]); });
-    }
-    return;
-  }
-  if (p.trans_out) {
-    int64_t bidx = m / p.trans_rows, mi = m % p.trans_rows;
-    TOut* base = C + bidx * (int64_t)p.N * p.trans_ld + mi;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (n + r < p.N) base[(int64_t)(n + r) * p.trans_ld] = from_f32<TOut>(v[r]);
-    return;
-  }
-  if constexpr (sizeof(TOut) == 2) {
-    if (p.split_out) {   // split-bf16 pair rows (no residual: checked on the host)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < p.N) {
-          const bf16_t hi = (bf16_t)v[r];
-          C[m * p.ldc + n + r] = hi;
-          C[m * p.ldc + p.N + n + r] = (bf16_t)(v[r] - (float)hi);
-        }
-      return;
-    }
-  }
-  const bool full = (n + 3 < p.N) && ((p.ldc & 3) == 0) && (res == nullptr || (p.ldr & 3) == 0);
-  if (full) {
-    if (res != nullptr) {
-      if constexpr (sizeof(TOut) == 4) {
-        f32x4 rv = *reinterpret_cast<const f32x4*>(res + m * p.ldr + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += rv[r];
-      } else {
-        bf16x4 rv = *reinterpret_cast<const bf16x4*>(res + m * p.ldr + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += (float)rv[r];
-      }
-    }
-    if constexpr (sizeof(TOut) == 4) {
-      f32x4 o = {v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<f32x4*>(C + m * p.ldc + n) = o;
-    } else {
-      bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-      *reinterpret_cast<bf16x4*>(C + m * p.ldc + n) = o;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (n + r < p.N) {
-        float o = v[r];
-        if (res != nullptr) o += to_f32(res[m * p.ldr + n + r]);
-        C[m * p.ldc + n + r] = from_f32<TOut>(o);
-      }
-    }
-  }
-}
-
-// bias + activation of the 4 consecutive-n values a lane holds for token m, then store4.
-template <typename TOut>
-__device__ __forceinline__ void epilogue_store(const GemmP& p, const float* bias, int64_t m, int n,
-                                               f32x4 acc) {
-  if (m >= p.M || n >= p.N) return;
-  float v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float b = 0.0f;
-    if (bias != nullptr) b = p.bias_m ? bias[m] : (n + r < p.N ? bias[n + r] : 0.0f);
-    v[r] = apply_act<TOut>(acc[r] + b, p.act);
-  }
-  store4<TOut>(p, m, n, v);
-}
-
-// bijective XCD remap: consecutive logical tile ids land on the same XCD (block b runs on XCD b%8)
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = bid & 7, idx = bid >> 3;
-  const int start = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return start + idx;
-}
 
 // ---------------------------------------------------------------------------------------------
 // gemm_dma<T,TOut,BM,BN>: the large-M GEMM (Swin / FPN / projection / K-V slabs).
@@ -228,22 +32,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 //     contiguous and leave as 16-byte stores of full 128/256-byte row segments, the residual arriving the
 //     same way -- instead of 8-byte stores scattered over 16 rows per instruction.
 // ---------------------------------------------------------------------------------------------
-// wait until at most `tiles` of this wave's most recently issued K tiles (IPT DMA instructions each) are
-// still in flight; the count must be an immediate, hence the switch (wave-uniform, so one scalar branch)
-template <int IPT>
-__device__ __forceinline__ void wait_dma_tiles(int tiles) {
-  static_assert(IPT * 7 <= 63, "vmcnt immediate out of range");
-  switch (tiles) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 1) : "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 2) : "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 3) : "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 4) : "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 5) : "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 6) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPT * 7) : "memory"); break;
-  }
-}
 
 template <typename T, typename TOut, int BM, int BN, int NS, bool TRACE = false>
 __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
@@ -558,11 +346,6 @@ int launch_dma(GemmP& p, hipStream_t st) {
   return OMP_OK;
 }
 
-#include "gemm256.inc"
-#include "gemm4w.inc"
-#include "gemm4wr.inc"
-#include "gemm4wp.inc"
-
 template <typename T, typename TOut>
 __global__ __launch_bounds__(256) void gemm_rows(GemmP p) {
   typedef Mma<T> MM;
@@ -812,9 +595,9 @@ constexpr GemmSel GEMM_SELECTORS[] = {
      "M <= 64, K a multiple of four k-steps (bf16: 128, fp32: 64), no trans_out, no split-bf16 operands / destinations, K <= 1024 behind the fused LayerNorm"},
     {5, "128x128 tiles", false, GEMM_OUT_ANY, true, true, 0, nullptr, ""},
     {6, "64x64 tiles", false, GEMM_OUT_ANY, true, false, 0, nullptr, ""},
-    {9, "256x256 tiles (gemm256.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm256_ok,
+    {9, "256x256 tiles (gemm256.hip)", true, GEMM_OUT_ANY, true, true, 0, gemm256_ok,
      "K % 64 == 0, K >= 128, N % 8 == 0 (blocked K / V^T slabs: bf16 only)"},
-    {10, "256x256 tiles on four waves (gemm4w.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4w_ok, "the shapes of selector 9"},
+    {10, "256x256 tiles on four waves (gemm4w.hip)", true, GEMM_OUT_ANY, true, true, 0, gemm4w_ok, "the shapes of selector 9"},
     {11, "256x256 tiles on four waves; alias of 10", true, GEMM_OUT_ANY, true, true, 0, gemm4w_ok, "the shapes of selector 9"},
     // development: gemm_4w ablations (wrong results, valid timing), plain bf16 destination only
     {12, "gemm_4w ablation 1", true, GEMM_OUT_BF16, false, false, 0, gemm4w_plain_ok, "plain bf16 products"},
@@ -822,18 +605,18 @@ constexpr GemmSel GEMM_SELECTORS[] = {
     {14, "gemm_4w ablation 3", true, GEMM_OUT_BF16, false, false, 0, gemm4w_plain_ok, "plain bf16 products"},
     // development: gemm_dma<128,128,2> with per-workgroup phase timestamps
     {15, "128x128 tiles with timestamps", false, GEMM_OUT_ANY, true, false, 128, nullptr, ""},
-    // 256x256 tiles on four waves, weights streamed into registers (gemm4wr.inc); 17: without its MFMAs (wrong results, valid timing);
+    // 256x256 tiles on four waves, weights streamed into registers (gemm4wr.hip); 17: without its MFMAs (wrong results, valid timing);
     // 18: per-workgroup phase timestamps (tools/gemm4wr_trace.py)
-    {16, "register-streamed weights (gemm4wr.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4wr_ok,
+    {16, "register-streamed weights (gemm4wr.hip)", true, GEMM_OUT_ANY, true, true, 0, gemm4wr_ok,
      "row-major destinations of selector 9 with K % 256 == 0"},
     {17, "register-streamed weights without MFMAs", true, GEMM_OUT_BF16, false, true, 0, gemm4wr_plain_ok, "plain bf16 products of selector 16"},
     {18, "register-streamed weights with timestamps", true, GEMM_OUT_ANY, true, true, 256, gemm4wr_ok,
      "row-major destinations of selector 9 with K % 256 == 0"},
-    // persistent 256x256 tiles on four waves, register-only epilogue (gemm4wp.inc); 21: 2/3 of its operand bytes (wrong results, valid timing)
-    {20, "persistent four-wave tiles (gemm4wp.inc)", true, GEMM_OUT_ANY, true, true, 0, gemm4wp_ok,
+    // persistent 256x256 tiles on four waves, register-only epilogue (gemm4wp.hip); 21: 2/3 of its operand bytes (wrong results, valid timing)
+    {20, "persistent four-wave tiles (gemm4wp.hip)", true, GEMM_OUT_ANY, true, true, 0, gemm4wp_ok,
      "row-major destinations with M, N, K multiples of 256 and 16-byte aligned bias / rows"},
     {21, "persistent four-wave tiles, 2/3 of the operand bytes", true, GEMM_OUT_F32, true, true, 0, gemm4wp_ok, "the fp32 products of selector 20"},
-    // bf16x3: the three products fused over shared operand tiles (gemm4wp.inc, X3)
+    // bf16x3: the three products fused over shared operand tiles (gemm4wp.hip, X3)
     {22, "fused bf16x3 products", true, GEMM_OUT_ANY, true, true, 0, gemm4wx3_ok,
      "bf16x3 operands (a_wrap = 2 K0, K = 3 K0, K0 % 128 == 0), M and N multiples of 256, fp32 or split destination"},
 };
@@ -874,11 +657,11 @@ inline int gemm_auto_select(const GemmP& p, bool bf16_in, bool bf16_out) {
     const int64_t t256 = ceil_div64(p.M, 256) * ceil_div64(p.N, 256);
     const bool fills = t256 >= 192 && 4 * t256 >= 3 * 256 * ceil_div64(t256, 256);
     if (which == 5 && p.N >= 256 && fills && gemm256_ok(p, true, bf16_out)) which = 9;
-    // the four-wave kernel (gemm4w.inc) produces the same bits; measured against gemm_256 per shape (profiles/r04f_kbench_gemm_4w_v2_*):
+    // the four-wave kernel (gemm4w.hip) produces the same bits; measured against gemm_256 per shape (profiles/r04f_kbench_gemm_4w_v2_*):
     // equal within the box-to-box spread on most, 7-13 % faster on the half-million-row products of stage 1 without an activation,
     // 7-13 % slower behind a GELU epilogue (four waves instead of eight do the vector work) -- it takes the former
     if (which == 9 && p.act == OMP_ACT_NONE && p.store_mode == OMP_STORE_PLAIN && p.M >= 262144 && (p.K >= 1024 || p.N >= 768)) which = 10;
-    // the persistent four-wave kernel (gemm4wp.inc; same bits again) where its register-only epilogue and its missing prologues pay
+    // the persistent four-wave kernel (gemm4wp.hip; same bits again) where its register-only epilogue and its missing prologues pay
     // (profiles/r04s_kbench_gemm_4w_p_*.txt, r04v_kbench_ab_k9_k20.txt: three boxes): behind a GELU on a bf16 destination (+9 % at
     // K = 512, +3-13 % at K = 768, +23-30 % at K = 256, equal at K = 1024) and on the K = 768 products without a residual (ViT-B qkv
     // +7 %, the bf16x3 stage-1 qkv +7 % over gemm_4w); equal or behind gemm_256 elsewhere (K = 256 without GELU: +12 % on one box,
@@ -886,7 +669,7 @@ inline int gemm_auto_select(const GemmP& p, bool bf16_in, bool bf16_out) {
     if ((which == 9 || which == 10) && !p.split_out && gemm4wp_ok(p, true, bf16_out) &&
         ((p.act == OMP_ACT_GELU && bf16_out) || (p.K == 768 && p.residual == nullptr && p.N >= 768 && p.act == OMP_ACT_NONE)))
       which = 20;
-    // bf16x3 operands: the three products fused over shared operand tiles (gemm4wp.inc, X3) wherever a 256x256-tile kernel was chosen
+    // bf16x3 operands: the three products fused over shared operand tiles (gemm4wp.hip, X3) wherever a 256x256-tile kernel was chosen
     // and the shape has no ragged edge -- 2/3 of the operand bytes; faster on every encoder product of the parity engine
     // (profiles/r04y_kbench_gemm_x3_fused.txt: -1...-17 %).  Its summation order is chunk by chunk, not plane by plane: equal to the
     // three-pass kernels within fp32 rounding, not bit for bit.
@@ -895,40 +678,36 @@ inline int gemm_auto_select(const GemmP& p, bool bf16_in, bool bf16_out) {
   return which;
 }
 
-// the launch of selector `which` (4 excepted: launch_gemm calls launch_small itself): a switch of direct calls (the few-row decoder step is bound by its launch rate and comes through here)
+// the launch of selector `which` (4 excepted: launch_gemm calls launch_small itself).  3, 5, 6 and 15 are direct calls inside this unit (the few-row decoder step
+// is bound by its launch rate and comes through here); the tile kernels are launched through the entry point of their unit (gemm_common.h)
 template <typename T, typename TOut>
 int gemm_launch_sel(int which, GemmP& p, hipStream_t st) {
   constexpr bool BI = std::is_same<T, bf16_t>::value, BO = std::is_same<TOut, bf16_t>::value;
-  // (cases in the order the kernels have always been instantiated in: it is their order in the code object, which kept the device code of this
-  // file identical across the move to the table.  Nothing else depends on it: sort the cases whenever that proof is no longer wanted.)
   switch (which) {
+    case 3: {
+      dim3 grid((unsigned)ceil_div64(p.N, 64), (unsigned)ceil_div64(p.M, 16));
+      hipLaunchKernelGGL((gemm_rows<T, TOut>), grid, dim3(256), 0, st, p);
+      return OMP_OK;
+    }
     case 5: return launch_dma<T, TOut, 128, 128, 2>(p, st);
     case 6:
       // mid-size problems (decoder phases with 65..~4000 rows, small-image encoders): 64x64 tiles and a deep
       // ring so that the K extent is in flight at once; a shallower ring (2 workgroups per CU) once the grid
       // is large enough to want the occupancy instead
       return (ceil_div64(p.M, 64) * ceil_div64(p.N, 64) <= 512) ? launch_dma<T, TOut, 64, 64, 8>(p, st) : launch_dma<T, TOut, 64, 64, 4>(p, st);
-    case 9: if constexpr (BI) return launch_256<TOut>(p, st); break;
-    case 10: case 11: if constexpr (BI) return launch_4w<TOut, 5>(p, st); break;
-    case 12: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 1>(p, st); break;
-    case 13: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 2>(p, st); break;
-    case 14: if constexpr (BI && BO) return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, 5, 3>(p, st); break;
-    case 16: if constexpr (BI) return launch_4wr<TOut>(p, st); break;
-    case 18: if constexpr (BI) return launch_4wr_t<TOut, false, 4>(p, st); break;
-    case 17: if constexpr (BI && BO) return launch_4wr_t<TOut, false, 3>(p, st); break;
-    case 20: if constexpr (BI) return launch_4wp<TOut>(p, st); break;
-    case 21: if constexpr (BI && !BO) return launch_4wp_t<TOut, false, 5>(p, st); break;
-    case 22: if constexpr (BI) return launch_4wx3<TOut>(p, st); break;
+    case 9: if constexpr (BI) return gemm256_launch(p, !BO, st); break;
+    case 10: case 11: if constexpr (BI) return gemm4w_launch(p, !BO, st); break;
+    case 12: case 13: case 14: if constexpr (BI) return gemm4w_launch_ablation(p, !BO, st, which - 11); break;
     case 15: return launch_dma<T, TOut, 128, 128, 2, true>(p, st);
-    case 3: {
-      dim3 grid((unsigned)ceil_div64(p.N, 64), (unsigned)ceil_div64(p.M, 16));
-      hipLaunchKernelGGL((gemm_rows<T, TOut>), grid, dim3(256), 0, st, p);
-      return OMP_OK;
-    }
+    case 16: if constexpr (BI) return gemm4wr_launch(p, !BO, st); break;
+    case 17: if constexpr (BI) return gemm4wr_launch_dev(p, !BO, st, 3); break;
+    case 18: if constexpr (BI) return gemm4wr_launch_dev(p, !BO, st, 4); break;
+    case 20: if constexpr (BI) return gemm4wp_launch(p, !BO, st); break;
+    case 21: if constexpr (BI) return gemm4wp_launch_ablation(p, !BO, st, 5); break;
+    case 22: if constexpr (BI) return gemm4wx3_launch(p, !BO, st); break;
     default: break;
   }
-  omp_set_error("omp_gemm_bias_act: kernel selector %d is not built for these types", which);   // gemm_accepts refuses them first
-  return OMP_ERR_INVALID;
+  return gemm_not_built(which);
 }
 
 template <typename T, typename TOut>
@@ -970,6 +749,9 @@ int launch_gemm(const GemmP& p0, hipStream_t st) {
 }
 
 }  // namespace
+}  // namespace omp_gemm
+
+using namespace omp_gemm;
 
 extern "C" int omp_debug_set_gemm_trace(void* buffer, int64_t n_workgroups) {
   omp_cur().gemm_trace = reinterpret_cast<unsigned long long*>(buffer);

@@ -1,6 +1,6 @@
-// gemm_256<TOut>: the large-N Swin GEMMs (qkv, fc1, fc2) on 256x256x64 tiles -- included by gemm.hip inside its namespace.
+// gemm_256<TOut>: the large-N Swin GEMMs (qkv, fc1, fc2) on 256x256x64 tiles (selector 9; a unit of its own).
 //
-// The 128x128 kernel above tops out near 30 % of the bf16 matrix-core peak on these shapes: two co-resident
+// The 128x128 kernel (gemm_dma, gemm.hip) tops out near 30 % of the bf16 matrix-core peak on these shapes: two co-resident
 // workgroups hide each other's DMA round trips, but every K tile still costs a full barrier + fragment-read
 // restart, and a 128x128 tile moves twice the operand bytes per flop through L2 -> LDS.  This kernel follows the
 // phase-interleaved schedule of the CDNA4 playbook (cdna_hip_programming.md, "256^2 8-phase template"), restated for
@@ -25,6 +25,11 @@
 
 // TOut = bf16 or float (fp32 residual streams / fp32 consumers); SPLIT (TOut = bf16, plain store): the result leaves as a
 // split-bf16 pair row [hi | lo] (OMP_BF16X2: hi at column n, lo at column N + n), the storage format of the bf16x3 engine.
+#include "gemm_common.h"
+
+namespace omp_gemm {
+namespace {
+
 template <typename TOut, int SM, bool SPLIT = false>   // SM: OMP_STORE_PLAIN, or the blocked K / V^T slabs of the cross-attention memory
 __global__ __launch_bounds__(512, 2) void gemm_256(GemmP p) {
   typedef bf16_t T;
@@ -367,18 +372,8 @@ int launch_256(GemmP& p, hipStream_t st) {
   return launch_256_sm<TOut, OMP_STORE_PLAIN>(p, st);
 }
 
-// shapes this kernel takes (everything else stays on gemm_dma)
-inline bool gemm256_ok(const GemmP& p, bool bf16_in, bool bf16_out) {
-  if (!(bf16_in && !p.trans_out && (p.bias_row == nullptr || (p.bias_row_stride % 4) == 0) && p.ln_g == nullptr && p.K % 64 == 0 && p.K >= 128 && p.N % 8 == 0 &&
-        (p.a_wrap == 0 || p.a_wrap % 64 == 0)))
-    return false;
-  if (p.store_mode == OMP_STORE_PLAIN)
-    return !p.bias_m && (p.ldc % 8) == 0 && (p.residual == nullptr || (p.ldr % 8) == 0) && (p.C2 == nullptr || (p.ldc2 % 8) == 0) &&
-           (!p.split_out || (bf16_out && p.residual == nullptr));
-  if (!bf16_out) return false;
-  // blocked cross-attention memory (bf16 or split planes): 32-key blocks, whole 8-token chunks inside one image, no residual / activation
-  if (p.kv_kb != 32 || p.residual != nullptr || p.act != OMP_ACT_NONE || p.C2 != nullptr) return false;
-  if (p.store_mode == OMP_STORE_KBLK) return !p.bias_m && p.N % 64 == 0;
-  if (p.store_mode == OMP_STORE_VBLK) return (p.bias == nullptr || p.bias_m) && p.kv_tok % 8 == 0;
-  return false;
-}
+}  // namespace
+
+int gemm256_launch(GemmP& p, bool f32_out, hipStream_t st) { return f32_out ? launch_256<float>(p, st) : launch_256<bf16_t>(p, st); }
+
+}  // namespace omp_gemm

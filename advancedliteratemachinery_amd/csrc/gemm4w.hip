@@ -1,7 +1,7 @@
-// gemm_4w<TOut>: 256x256 output tiles on FOUR waves (one per SIMD), 256 accumulator registers each -- included by gemm.hip inside its
-// namespace (round 4).
+// gemm_4w<TOut>: 256x256 output tiles on FOUR waves (one per SIMD), 256 accumulator registers each (selectors 10 .. 14; a unit of
+// its own; round 4).
 //
-// gemm_256 (gemm256.inc) keeps a 256x256 tile on EIGHT waves of 128x64: per 64-deep K tile every wave reads 24 operand fragments
+// gemm_256 (gemm256.hip) keeps a 256x256 tile on EIGHT waves of 128x64: per 64-deep K tile every wave reads 24 operand fragments
 // for 64 matrix-core instructions (192 KB of ds_read per K tile and CU) and synchronises the workgroup eight times per K tile.  Here a
 // wave owns 128x128 (8 x 8 blocks of 16x16, 64 accumulator quads = the whole accumulator file; one wave per SIMD), so a 32-deep K
 // stage costs 16 fragment reads for 64 MFMAs (128 KB per 64 of K) and ONE barrier:
@@ -22,20 +22,14 @@
 //   * epilogue through LDS in two 64-token passes per wave (wave-private 64 x 132 fp32 regions over the drained ring), bias /
 //     activation / residual / 16-byte row-contiguous stores exactly as gemm_256.
 // bf16 operands, bf16 / fp32 / split-bf16 row-major destination or the blocked K / V^T slabs, K % 64 == 0, N % 8 == 0.
-template <int... I, class F>
-__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>()), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>(), f); }
-
-// the 256 accumulator registers by name (asm clobber list: the kernel descriptor then allocates them and the compiler keeps out)
-#define OMP_A4(n) "a" #n "0", "a" #n "1", "a" #n "2", "a" #n "3", "a" #n "4", "a" #n "5", "a" #n "6", "a" #n "7", "a" #n "8", "a" #n "9"
-#define OMP_ALL_AGPRS                                                                                                                   \
-  "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", OMP_A4(1), OMP_A4(2), OMP_A4(3), OMP_A4(4), OMP_A4(5), OMP_A4(6), OMP_A4(7),   \
-      OMP_A4(8), OMP_A4(9), OMP_A4(10), OMP_A4(11), OMP_A4(12), OMP_A4(13), OMP_A4(14), OMP_A4(15), OMP_A4(16), OMP_A4(17), OMP_A4(18), \
-      OMP_A4(19), OMP_A4(20), OMP_A4(21), OMP_A4(22), OMP_A4(23), OMP_A4(24), "a250", "a251", "a252", "a253", "a254", "a255"
 
 // ABL (development, selectors 12..14: wrong results, valid timing): 1 = no DMA in the main loop, 2 = no fragment reads, 3 = no MFMAs --
 // which resource paces the loop (profiles/r04e_gemm4w_ablation.txt)
+#include "gemm_common.h"
+
+namespace omp_gemm {
+namespace {
+
 template <typename TOut, int SM, bool SPLIT, int NS, int ABL = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_4w(GemmP p) {
   typedef bf16_t T;
@@ -410,12 +404,17 @@ int launch_4w(GemmP& p, hipStream_t st) {
   return launch_4w_sm<TOut, OMP_STORE_PLAIN, false, NS>(p, st);
 }
 
-// shapes this kernel takes: those of gemm_256 (its stages are 32 deep, but the library's K granularity stays 64) and K = 64
-inline bool gemm4w_ok(const GemmP& p, bool bf16_in, bool bf16_out) {
-  if (p.K == 64) {   // two stages: fewer than the ring holds, handled by the prologue / tail guards
-    GemmP q = p;
-    q.K = 128;
-    return gemm256_ok(q, bf16_in, bf16_out);
+}  // namespace
+
+int gemm4w_launch(GemmP& p, bool f32_out, hipStream_t st) { return f32_out ? launch_4w<float, 5>(p, st) : launch_4w<bf16_t, 5>(p, st); }
+
+int gemm4w_launch_ablation(GemmP& p, bool f32_out, hipStream_t st, int abl) {
+  if (!f32_out) {
+    if (abl == 1) return launch_4w_sm<bf16_t, OMP_STORE_PLAIN, false, 5, 1>(p, st);
+    if (abl == 2) return launch_4w_sm<bf16_t, OMP_STORE_PLAIN, false, 5, 2>(p, st);
+    if (abl == 3) return launch_4w_sm<bf16_t, OMP_STORE_PLAIN, false, 5, 3>(p, st);
   }
-  return gemm256_ok(p, bf16_in, bf16_out);
+  return gemm_not_built(11 + abl);
 }
+
+}  // namespace omp_gemm

@@ -1,4 +1,4 @@
-// gemm_4w_p<TOut>: gemm_4w_r made PERSISTENT -- included by gemm.hip inside its namespace, after gemm4wr.inc (round 4).
+// gemm_4w_p<TOut>: gemm_4w_r made PERSISTENT (gemm4wr.hip; selectors 20 .. 22; a unit of its own; round 4).
 //
 // tools/gemm4wr_trace.py (profiles/r04r_gemm4wr_trace.txt) timed the phases of a 256x256 tile with one workgroup per CU, K = 512, bf16
 // destination: 13.9 k cycles from the first instruction to "X tile 0 landed", 20.7 k in the main loop (16.4 k of MFMAs), 12.6 k in the
@@ -26,6 +26,11 @@
 // 64-deep chunk c of K0 is three sub-stages over two X tiles and two W fragment sets: (W_hi, X_hi), (W_hi, X_lo), (W_lo, X_hi) -- 2/3 of
 // the operand bytes, 2/3 of the requests, two barriers per three sub-stages.  The summation order differs from the three-pass kernels
 // (chunk by chunk instead of plane by plane): equal to them within fp32 rounding, not bit for bit.  K0 % 128 == 0.
+#include "gemm_common.h"
+
+namespace omp_gemm {
+namespace {
+
 template <typename TOut, bool SPLIT, int ABL = 0, bool X3 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_4w_p(GemmP p) {
   typedef bf16_t T;
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const unsigned woff = (unsigned)((((int64_t)(wave * 64 + lrow)) * p.ldw + lg * 8) * 2);   // feature block a: + 16 a rows in the scalar base
   const int64_t wblock = 16 * p.ldw * 2;
   frag fwr[4][8];   // [ring slot = stage & 3][k step * 4 + feature block]
-  // asm loads, waits counted by hand (gemm4wr.inc: hipcc drains the pipeline in front of loads that stay in flight across a back edge)
+  // asm loads, waits counted by hand (gemm4wr.hip: hipcc drains the pipeline in front of loads that stay in flight across a back edge)
   auto load_w = [&](const char* src, auto SL, auto IDX, bool thin = false) {
     constexpr int sl = decltype(SL)::value, idx = decltype(IDX)::value, a = idx >> 1, k = idx & 1;
     frag& dst = fwr[sl][k * 4 + a];
@@ -397,26 +402,21 @@ int launch_4wp(GemmP& p, hipStream_t st) {
   return launch_4wp_t<TOut, false>(p, st);
 }
 
-// shapes this kernel takes: gemm_4w_r's without ragged edges, bias readable as 16-byte vectors
-inline bool gemm4wp_ok(const GemmP& p, bool bf16_in, bool bf16_out) {
-  if (!gemm4wr_ok(p, bf16_in, bf16_out)) return false;
-  if (p.M % 256 != 0 || p.N % 256 != 0) return false;
-  if (p.bias != nullptr && ((reinterpret_cast<uintptr_t>(p.bias) & 15) != 0 || (p.bias_row != nullptr && p.bias_row_stride % 4 != 0))) return false;
-  const int esz = bf16_out ? 2 : 4;
-  if ((reinterpret_cast<uintptr_t>(p.C) % (4 * esz)) != 0 || (p.ldc * esz) % (4 * esz) != 0) return false;
-  if (p.residual != nullptr && ((reinterpret_cast<uintptr_t>(p.residual) % (4 * esz)) != 0 || p.ldr % 4 != 0)) return false;
-  if (p.C2 != nullptr && ((reinterpret_cast<uintptr_t>(p.C2) % (4 * esz)) != 0 || p.ldc2 % 4 != 0)) return false;
-  return true;
-}
-
-// the fused three-product kernel (X3): bf16x3 operands of a shape gemm_4w_p takes (K = 3 K0 a multiple of 256, i.e. K0 % 256 == 0; the
-// kernel itself needs an even number of 64-deep chunks, K0 % 128 == 0)
-inline bool gemm4wx3_ok(const GemmP& p, bool bf16_in, bool bf16_out) {
-  return p.a_wrap > 0 && (p.a_wrap % 2) == 0 && p.K == 3 * (p.a_wrap / 2) && (p.a_wrap / 2) % 128 == 0 && gemm4wp_ok(p, bf16_in, bf16_out) &&
-         (bf16_out ? p.split_out != 0 : true);
-}
 template <typename TOut>
 int launch_4wx3(GemmP& p, hipStream_t st) {
   if constexpr (sizeof(TOut) == 2) return launch_4wp_t<TOut, true, 0, true>(p, st);
   else return launch_4wp_t<TOut, false, 0, true>(p, st);
 }
+
+}  // namespace
+
+int gemm4wp_launch(GemmP& p, bool f32_out, hipStream_t st) { return f32_out ? launch_4wp<float>(p, st) : launch_4wp<bf16_t>(p, st); }
+
+int gemm4wp_launch_ablation(GemmP& p, bool f32_out, hipStream_t st, int abl) {
+  if (abl == 5 && f32_out) return launch_4wp_t<float, false, 5>(p, st);
+  return gemm_not_built(21);
+}
+
+int gemm4wx3_launch(GemmP& p, bool f32_out, hipStream_t st) { return f32_out ? launch_4wx3<float>(p, st) : launch_4wx3<bf16_t>(p, st); }
+
+}  // namespace omp_gemm

@@ -1,12 +1,12 @@
-// gemm_4w_r<TOut>: 256x256 output tiles on four waves with the WEIGHT operand streamed global -> registers -- included by gemm.hip
-// inside its namespace, after gemm4w.inc (round 4, the follow-up its ablation asked for: DESIGN.md section 10).
+// gemm_4w_r<TOut>: 256x256 output tiles on four waves with the WEIGHT operand streamed global -> registers (selectors 16 .. 18; a unit of
+// its own; round 4, the follow-up its ablation asked for: DESIGN.md section 10).
 //
 // The hypothesis it was built on (profiles/r04l_gemm4w_ablation_big_k.txt): the operand path of gemm_4w / gemm_256 alone (no MFMA) took
 // 1.3x the matrix-core time at 21 B/clk and CU of a 64 B/clk path -- bounded, it seemed, by the bytes in flight (48-64 KB of the 160 KB
 // ring per CU) times 1.1 us of L2 -> LDS latency.  LDS cannot hold more; the register file can.  RESULT (DESIGN.md section 10,
 // profiles/r04p_*, r04w_*): with 160 KB per CU requested the kernel is bit-exact and 3-8 % SLOWER than gemm_256 -- what is in flight is
 // bounded below the software, by the L1's request queue towards L2 (54-72 lines outstanding per CU at 460-570 cycles each).  The kernel
-// stays as the base of gemm_4w_p (gemm4wp.inc) and as the carrier of the no-MFMA ablation (17) and the phase trace (18).  The four
+// stays as the base of gemm_4w_p (gemm4wp.hip) and as the carrier of the no-MFMA ablation (17) and the phase trace (18).  The four
 // waves split the tile's FEATURES (wave w: all 256 tokens x features 64 w .. 64 w + 63), so
 //   * a wave's weight rows are its own: the 8 W fragments of a 64-deep K stage go straight from global memory into registers (the
 //     MFMA A operand of gemm_dma: lane = (feature l & 15, 16-byte k chunk l >> 4); the two fragments of a row's 128-byte line are
@@ -23,6 +23,11 @@
 //   * epilogue through LDS in four 64-token passes per wave (wave-private 64 x 68 fp32 regions over the drained ring), geometry and
 //     arithmetic of gemm_256's.
 // bf16 operands, bf16 / fp32 / split-bf16 row-major destination, K % 256 == 0, N % 8 == 0.
+#include "gemm_common.h"
+
+namespace omp_gemm {
+namespace {
+
 template <typename TOut, bool SPLIT, int ABL = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_4w_r(GemmP p) {
   typedef bf16_t T;
@@ -324,7 +329,14 @@ int launch_4wr(GemmP& p, hipStream_t st) {
   return launch_4wr_t<TOut, false>(p, st);
 }
 
-// shapes this kernel takes: row-major destinations of gemm_256 with K a multiple of four 64-deep stages
-inline bool gemm4wr_ok(const GemmP& p, bool bf16_in, bool bf16_out) {
-  return p.store_mode == OMP_STORE_PLAIN && p.K % 256 == 0 && gemm256_ok(p, bf16_in, bf16_out);
+}  // namespace
+
+int gemm4wr_launch(GemmP& p, bool f32_out, hipStream_t st) { return f32_out ? launch_4wr<float>(p, st) : launch_4wr<bf16_t>(p, st); }
+
+int gemm4wr_launch_dev(GemmP& p, bool f32_out, hipStream_t st, int abl) {
+  if (abl == 4) return f32_out ? launch_4wr_t<float, false, 4>(p, st) : launch_4wr_t<bf16_t, false, 4>(p, st);
+  if (abl == 3 && !f32_out) return launch_4wr_t<bf16_t, false, 3>(p, st);
+  return gemm_not_built(14 + abl);
 }
+
+}  // namespace omp_gemm

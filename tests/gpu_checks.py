@@ -1769,7 +1769,7 @@ def check_gemm_x3():
 
 
 def check_gemm_4w():
-    """gemm_4w (256x256 tiles on four waves, accumulators addressed literally in the accumulator file; csrc/gemm4w.inc), ring of 4
+    """gemm_4w (256x256 tiles on four waves, accumulators addressed literally in the accumulator file; csrc/gemm4w.hip), ring of 4
     and of 5 stages, against gemm_dma (k5) on the SAME operands: the kernels share the MFMA, the operand orientation and the
     ascending-k accumulation order, so every output must be equal BIT FOR BIT -- ragged M / N edges, K from 64 (fewer stages than
     the ring holds) to 6144, odd stage counts, bias / GELU / ReLU / bf16 and fp32 residual, second destination, per-position bias

@@ -1,4 +1,4 @@
-"""omp_gemm_bias_act (csrc/gemm.hip and its gemm*.inc files) at every ragged edge, pitch and few-row count: the 128x128 / 64x64 DMA tile
+"""omp_gemm_bias_act (csrc/gemm.hip and the tile-kernel units csrc/gemm256.hip, gemm4w.hip, gemm4wr.hip, gemm4wp.hip) at every ragged edge, pitch and few-row count: the 128x128 / 64x64 DMA tile
 kernels (selectors 5, 6), the 256x256 tile kernels (9, 10, 16, 20), gemm_rows (3) and the split-K gemm_small with its fused LayerNorm
 prologue (4), forced with ops.force_gemm_kernel.
 
@@ -401,7 +401,7 @@ def same_bits(out, name, a, b):
 
 
 def accepts(c):
-    """what the selector's *_ok predicate (and the host checks of omp_gemm_bias_act) take of a case, restated from csrc/gemm*.inc"""
+    """what the selector's *_ok predicate (and the host checks of omp_gemm_bias_act) take of a case, restated from csrc/gemm_common.h"""
     s, bf = c['sel'], c['dtn'] == 'bf16'
     if c['out'] == 'split' and (not bf or c['N'] % 8 or c['res'] or c['trans']):
         return False

@@ -105,10 +105,10 @@ def test_gemm4w_register_audit_catches_a_compiler_touch():
         with tempfile.NamedTemporaryFile('w', suffix='.s', delete=False) as f:
             f.write(text)
         try:
-            seen, bad = audit_gemm4w.audit(f.name)
+            seen, bad, checked = audit_gemm4w.audit(f.name)
         finally:
             os.unlink(f.name)
-        assert seen == 1 and len(bad) == n_bad, (seen, bad)
+        assert seen == 1 and len(bad) == n_bad and checked == 0, (seen, bad, checked)   # gemm_4w itself has no asm-loaded fragments: no stage-loop check
 
 
 def test_gemm4w_audit_refuses_a_register_copy_in_the_stage_loop():
@@ -126,10 +126,59 @@ def test_gemm4w_audit_refuses_a_register_copy_in_the_stage_loop():
         with tempfile.NamedTemporaryFile('w', suffix='.s', delete=False) as f:
             f.write(kernel(extra))
         try:
-            seen, bad = audit_gemm4w.audit(f.name)
+            seen, bad, checked = audit_gemm4w.audit(f.name)
         finally:
             os.unlink(f.name)
-        assert seen == 1 and len(bad) == n_bad, (extra, seen, bad)
+        assert seen == 1 and len(bad) == n_bad and checked == 1, (extra, seen, bad, checked)
+
+
+def _gemm4w_unit(names, extra=''):
+    """synthetic device assembly of a unit: one kernel per mangled name, each with a 512-MFMA innermost loop (+ extra inside it)"""
+    body = '\tv_mfma_f32_16x16x32_bf16 a[0:3], v[0:3], v[4:7], a[0:3]\n' * 512
+    text = ''
+    for i, name in enumerate(names):
+        text += ('%s: ; @k\n\ts_nop 0\n.LBB%d_2: ; %%loop\n ; =>This Inner Loop Header: Depth=1\n' % (name, i) + body + extra +
+                 '\ts_cbranch_scc1 .LBB%d_2\n; %%bb.3:\n\ts_endpgm\n' % i)
+    for name in names:
+        text += '  - .name:           %s\n    .agpr_count:     256\n    .private_segment_fixed_size: 0\n    .vgpr_spill_count: 0\n    .wavefront_size: 64\n' % name
+    return text
+
+
+def test_gemm4w_audit_recognises_production_kernels_of_the_split_units():
+    """csrc/gemm4wp.hip is a unit of its own and the parameter block lives in the named namespace omp_gemm: the production instantiations of
+    gemm_4w_p as hipcc mangles them there (kernel in the unit's anonymous namespace; GemmP as a substitution, or spelled out as it would be from
+    outside omp_gemm) are recognised and go through the stage-loop check, the ablation (ABL = 5) does not; a register copy in the loop of a
+    production kernel is still refused."""
+    from advancedliteratemachinery_amd import audit
+    import tempfile
+    prod = ['_ZN8omp_gemm12_GLOBAL__N_19gemm_4w_pIfLb0ELi0ELb0EEEvNS_5GemmPE', '_ZN8omp_gemm12_GLOBAL__N_19gemm_4w_pIDF16bLb1ELi0ELb1EEEvNS_5GemmPE',
+            '_ZN12_GLOBAL__N_19gemm_4w_pIDF16bLb0ELi0ELb0EEEvN8omp_gemm5GemmPE']
+    abl = ['_ZN8omp_gemm12_GLOBAL__N_19gemm_4w_pIfLb0ELi5ELb0EEEvNS_5GemmPE']
+    for extra, n_bad in (('', 0), ('\tv_mov_b32_e32 v1, v2\n', len(prod))):
+        with tempfile.NamedTemporaryFile('w', suffix='.s', delete=False) as f:
+            f.write(_gemm4w_unit(prod + abl, extra))
+        try:
+            seen, bad, checked = audit.audit_unit(f.name)
+        finally:
+            os.unlink(f.name)
+        assert seen == len(prod) + 1 and checked == len(prod) and len(bad) == n_bad, (extra, seen, checked, bad)
+
+
+def test_build_refuses_a_gemm4w_unit_whose_stage_loops_went_unchecked(tmp_path, monkeypatch):
+    """The audit finds the production kernels by their mangled names and skips what it does not recognise.  A unit of gemm_4w_r / gemm_4w_p
+    kernels of which NONE was recognised (here: the parameter block renamed) must not pass for want of anything to check: build.py's audit
+    step refuses it and leaves no audit stamp; the same unit under the names the audit knows passes and is stamped."""
+    import pytest
+    from advancedliteratemachinery_amd import build as B
+    monkeypatch.setattr(B, 'OBJ', str(tmp_path))
+    good = ['_ZN8omp_gemm12_GLOBAL__N_19gemm_4w_rIfLb0ELi0EEEvNS_5GemmPE', '_ZN8omp_gemm12_GLOBAL__N_19gemm_4w_rIDF16bLb1ELi0EEEvNS_5GemmPE']
+    open(B._asm_of('gemm4wr.hip'), 'w').write(_gemm4w_unit([n.replace('5GemmPE', '6GemmP2E') for n in good]))
+    with pytest.raises(RuntimeError, match='stage loop went unchecked'):
+        B._audit({'gemm4wr.hip': 'digest'})
+    assert not os.path.exists(str(tmp_path / 'gemm4wr.o.audit.stamp'))
+    open(B._asm_of('gemm4wr.hip'), 'w').write(_gemm4w_unit(good))
+    B._audit({'gemm4wr.hip': 'digest'})
+    assert open(str(tmp_path / 'gemm4wr.o.audit.stamp')).read() == 'digest'
 
 
 def test_rocpd_rate_bins_dispatches_per_window(tmp_path, capsys):

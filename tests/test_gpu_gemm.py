@@ -1,4 +1,4 @@
-"""GPU tests of omp_gemm_bias_act (csrc/gemm.hip, gemm*.inc) at every ragged edge, pitch and few-row count: sentinel-guarded destinations,
+"""GPU tests of omp_gemm_bias_act (csrc/gemm.hip, gemm256.hip, gemm4w.hip, gemm4wr.hip, gemm4wp.hip) at every ragged edge, pitch and few-row count: sentinel-guarded destinations,
 NaN-guarded operands, every K-tile count around each ring depth, every epilogue on vector and scalar pitches, bit equality of the 256x256
 kernels with the 128x128 kernel, every M from 1 to 64 through gemm_rows and gemm_small, the fused LayerNorm prologue with planted rows and
 two eps values, in place against out of place, clean refusals (tests/gpu_checks_gemm.py)."""

@@ -556,7 +556,7 @@ def test_split_plane_slab_indexing_is_a_bijection():
     """Round 4, the parity engine's K / V^T slabs: every 32-key block of an (image, head) slab is
     [hi plane | lo plane]; the element of key k, dim d, plane p sits at ((k // 32) * 2 + p) * 2048 + (k % 32) * 64 + d (K) and at
     ((k // 32) * 2 + p) * 2048 + d * 32 + slot(k % 32) (V^T, slot = the bf16 slab's matrix-core order) -- the formulas the GEMM
-    epilogues (csrc/gemm.hip::store4, gemm256.inc, gemm4w.inc) and the cross-attention kernels (csrc/decoder.hip, bf16s_t) share.
+    epilogues (csrc/gemm_common.h::store4, gemm256.hip, gemm4w.hip) and the cross-attention kernels (csrc/decoder.hip, bf16s_t) share.
     Both maps are bijections onto the slab and a value survives hi + lo to 2^-16 relative."""
     import numpy as np
     Mpad = 96
