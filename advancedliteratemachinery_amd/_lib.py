@@ -150,7 +150,8 @@ _SIGS = {
     'omp_reading_links': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3),
     'omp_reading_lines': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 9),
     'omp_reading_blocks': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 9),
-    'omp_ctx_create': (c_int, [ctypes.POINTER(c_void_p)]),
+    'omp_tile_remap': (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p] * 5 + [c_int] + [c_void_p] * 5),
+    'omp_ctx_create':(c_int, [ctypes.POINTER(c_void_p)]),
     'omp_ctx_destroy': (c_int, [c_void_p]),
     'omp_ctx_make_current': (c_int, [c_void_p]),
     'omp_ctx_current': (c_void_p, []),

@@ -15,6 +15,7 @@
 import json
 import os
 
+import numpy as np
 import torch
 import torch.distributed as tdist
 
@@ -152,6 +153,18 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     Every record gains `block` (its block within the image, in reading order from 0), `line` counts up through block 0, then block
     1, ..., `line_pos` stays, and each image's list comes in that order (utils.reading.page_blocks gives one string per block).  The
     two gap defaults are choices that no data set has tested.  Without blocks no new code runs."""
+    _check_stage_args(args, lexicon, suppress, suppress_measure, suppress_order, reading_order, line_gap, line_back, line_offset, blocks, block_gap_x,
+                      block_gap_y, block_depth)
+    out, raw_polys, sizes = _decode_records(model, images, args, targets, orig_sizes, ragged, windows, char_windows, clip_windows, grid)
+    if args.infer_vie:
+        return out
+    return _finish_records(model, out, raw_polys, sizes, args.num_bins, args, lexicon, lexicon_max_dist, lexicon_max_ratio, suppress, suppress_measure,
+                           suppress_order, reading_order, line_gap, line_back, line_offset, blocks, block_gap_x, block_gap_y, block_depth)
+
+
+def _check_stage_args(args, lexicon, suppress, suppress_measure, suppress_order, reading_order, line_gap, line_back, line_offset, blocks, block_gap_x,
+                      block_gap_y, block_depth):
+    """the refusals of predict's post-processing arguments, ahead of any device work"""
     if blocks and not reading_order:
         raise ValueError('blocks=True orders the lines of reading_order=True: pass both')
     if reading_order:
@@ -162,6 +175,12 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
         OV.check_suppress_args(suppress, suppress_measure, suppress_order, args.infer_vie)
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+
+
+def _decode_records(model, images, args, targets, orig_sizes, ragged, windows, char_windows, clip_windows, grid, want_points=False):
+    """predict's first part: the engine call and decode_pred_seq -> (records per image, the polygon decoder's raw ids per image -- device
+    tensors, None for an image without a result --, orig_size per image); with args.infer_vie (the entity tuples per image, None, None).
+    want_points: a fourth value, the point decoder's raw ids per image."""
     if orig_sizes is None and targets is not None and args.infer_vie:
         orig_sizes = [t['orig_size'] for t in targets]
     per_image = None
@@ -175,7 +194,7 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
     wkw = {} if per_image is None else dict(windows=per_image, char_windows=char_windows, clip_windows=clip_windows)
     raw, nt = predict_raw(model, images, args, orig_sizes, ragged=ragged, **wkw)
     if args.infer_vie:
-        return [r if r is not None else [] for r in raw]
+        return [r if r is not None else [] for r in raw], None, None
     out, sizes = [], []
     for b, r in enumerate(raw):
         tgt = (targets[b] if targets is not None else
@@ -189,13 +208,26 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
         if per_image is not None:
             for rcd, w in zip(out[-1], r[2].tolist()):
                 rcd['window'], rcd['window_bins'] = int(w), list(per_image[b][w])
+    raw_polys = [None if r is None else r[0][1] for r in raw]
+    if want_points:
+        return out, raw_polys, sizes, [None if r is None else r[0][0] for r in raw]
+    return out, raw_polys, sizes
+
+
+def _finish_records(model, out, raw_polys, sizes, grid, args, lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, suppress=None,
+                    suppress_measure='iou', suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5, blocks=False,
+                    block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
+    """predict's second part: suppress=, reading_order= / blocks= and lexicon= on the records of one list per image, whose polygons are
+    raw_polys on a grid of `grid` bins and whose sizes are `sizes` -- the images of a plain call, the pages of a tiled one"""
     rows = None
     if suppress is not None:
+        from ..utils import overlap as OV
         rows = []
-        out = OV.suppress_records(out, [None if r is None else r[0][1] for r in raw], args.num_bins, suppress, suppress_measure, suppress_order,
+        out = OV.suppress_records(out, raw_polys, grid, suppress, suppress_measure, suppress_order,
                                   device=next(model.parameters()).device, kept_rows=rows)
     if reading_order:
-        out = RD.order_records(out, [None if r is None else r[0][1] for r in raw], sizes, args.num_bins, line_gap, line_back, line_offset, rows=rows,
+        from ..utils import reading as RD
+        out = RD.order_records(out, raw_polys, sizes, grid, line_gap, line_back, line_offset, rows=rows,
                                device=next(model.parameters()).device, blocks=blocks, block_gap_x=block_gap_x, block_gap_y=block_gap_y,
                                block_depth=block_depth)
     if lexicon is not None:
@@ -209,7 +241,7 @@ def predict(model, images, args, targets=None, orig_sizes=None, ragged=False, le
 def predict_images(model, images_u8, args, file_names=None, preprocessor=None, ragged=False, lexicon=None, lexicon_max_dist=None,
                    lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False, grid=None, suppress=None, suppress_measure='iou',
                    suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5, line_offset=0.5, blocks=False, block_gap_x=1.0,
-                   block_gap_y=1.5, block_depth=8):
+                   block_gap_y=1.5, block_depth=8, tiles=None, tile_size=None, tile_overlap=0.125, tile_edge=2, tile_cut='drop', page_bins=None):
     """Raw images in, records out: uint8 RGB [H, W, 3] arrays / tensors -> the reference's val transform chain on the
     device (utils/preprocess.py: aspect-preserving Pillow-exact resize to test_min_size / test_max_size, ToTensor,
     Normalize, pad + mask) -> the hot path -> records in ORIGINAL image coordinates (val.py:70-100).
@@ -221,8 +253,30 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     reading_order, line_gap, line_back, line_offset: as predict (records gain `line`, `line_pos` and come in reading order); the
     aspect of every image is that of the ORIGINAL image, whose size scales the polygons.
     blocks, block_gap_x, block_gap_y, block_depth: as predict (records gain `block`; needs reading_order=True).
+    tiles=(nx, ny) or tile_size=s (nx = ceil(width / s), ny = ceil(height / s) per page), tile_overlap, tile_edge, tile_cut, page_bins:
+    tiled pages (utils/tiles.py) -- a page larger than the model's input is not scaled down as a whole: it is cut
+    into nx * ny overlapping tiles (utils.tiles.plan_tiles: the cores partition the page, every tile is its core grown by ox =
+    ceil(width / nx) * tile_overlap pixels and oy likewise, so neighbours share 2 ox pixels), every tile is resized on its own to
+    test_min_size / test_max_size, and the tiles of ALL pages are read in ONE engine flow as views of the page images.  ragged= is
+    honoured as given; ragged=True is recommended, since only then a tile's words do not depend on the other tiles of the call.  One
+    device call (omp_tile_remap) then carries the words into page bins -- a grid of page_bins bins over the page, default min(4096,
+    num_bins * max(nx, ny)) over the call's pages --, flags the words that reach within tile_edge tile bins of an INNER side of their
+    tile (a fragment of a word the neighbouring tile sees whole) and, with tile_cut='drop', removes them; 'keep' returns them too.  The
+    records come per PAGE, tiles in x-outer order and inside a tile in the decoder's order, `pts` / `polys` in page pixels, and gain
+    `tile` (index within the page), `tile_rect` ([x0, y0, x1, y1], pixels) and `tile_cut` (bits 1 left, 2 top, 4 right, 8 bottom).
+    suppress=, reading_order= / blocks= and lexicon= then run on the PAGES: on the page-bin polygons with grid = page_bins, the pages'
+    sizes and one group per page; `merged` indices count a page's records after the tile stage.  suppress= removes the doubles of
+    the words that lie whole in two tiles' shared strip.  A word longer than 2 ox pixels (2 oy for a vertical one) fits no shared
+    strip: it is cut in BOTH of its tiles and is lost under 'drop'; 'keep' returns both fragments, flagged.  windows= / grid= compose
+    in their shared form (every tile is read under the same windows; one window list per image is refused); KIE is refused.  The
+    defaults of tile_overlap, tile_edge and page_bins are choices that no data set has tested.  Without tiles= / tile_size= no new
+    code runs and the records are the plain call's.
     Returns (results per image, preprocessor) so the coefficient tables can be reused by the next call."""
     from ..utils.preprocess import DevicePreprocessor
+    tkw = None
+    if tiles is not None or tile_size is not None:
+        from ..utils import tiles as TL
+        tkw = TL.check_tile_args(tiles, tile_size, tile_overlap, tile_edge, tile_cut, page_bins, args.num_bins, args.infer_vie, windows)
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
     skw = {}
@@ -242,12 +296,47 @@ def predict_images(model, images_u8, args, file_names=None, preprocessor=None, r
     if preprocessor is None:
         preprocessor = DevicePreprocessor(args.test_min_size, args.test_max_size, dev)
     imgs = [torch.as_tensor(i).to(dev) for i in images_u8]
+    if tkw is not None:
+        return _predict_tiled(model, imgs, args, file_names, preprocessor, ragged, lexicon, lexicon_max_dist, lexicon_max_ratio, windows, char_windows,
+                              clip_windows, grid, skw, tiles, tile_size, tkw), preprocessor
     nt, _ = preprocessor(imgs)
     targets = [{'file_name': (file_names[b] if file_names is not None else str(b)),
                 'orig_size': (int(im.shape[0]), int(im.shape[1]))} for b, im in enumerate(imgs)]
     return predict(model, nt, args, targets=targets, orig_sizes=[t['orig_size'] for t in targets], ragged=ragged, lexicon=lexicon,
                    lexicon_max_dist=lexicon_max_dist, lexicon_max_ratio=lexicon_max_ratio, windows=windows, char_windows=char_windows,
                    clip_windows=clip_windows, grid=grid, **skw), preprocessor
+
+
+def _predict_tiled(model, imgs, args, file_names, preprocessor, ragged, lexicon, lexicon_max_dist, lexicon_max_ratio, windows, char_windows,
+                   clip_windows, grid, skw, tiles, tile_size, tkw):
+    """predict_images with tiles= / tile_size=: the tiles of all pages through predict's first part in ONE flow, the tile stage, predict's
+    second part on the pages"""
+    from ..utils import tiles as TL
+    dev = next(model.parameters()).device
+    page_hw = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+    names = [file_names[p] if file_names is not None else str(p) for p in range(len(imgs))]
+    rect, owner, page_size, grids = TL.plan_pages(page_hw, tiles, tile_size, tkw['o'])
+    P = tkw['page_bins'] if tkw['page_bins'] is not None else TL.default_page_bins(args.num_bins, grids)
+    if len(imgs) == 0:
+        return []
+    views = [imgs[p][y0:y1, x0:x1] for p, (x0, y0, x1, y1) in zip(owner.tolist(), rect.tolist())]     # no copy: the preprocessor takes the pitch
+    nt, _ = preprocessor(views)
+    targets = [{'file_name': names[p], 'orig_size': (y1 - y0, x1 - x0)} for p, (x0, y0, x1, y1) in zip(owner.tolist(), rect.tolist())]
+    recs, raw_polys, _, raw_points = _decode_records(model, nt, args, targets, [t['orig_size'] for t in targets], ragged, windows, char_windows,
+                                                     clip_windows, grid, want_points=True)
+    counts = [len(r) for r in recs]
+    row_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    polys = [torch.as_tensor(raw_polys[k]).reshape(-1, 32)[:n] for k, n in enumerate(counts) if n]
+    points = [torch.as_tensor(raw_points[k]).reshape(-1)[:2 * n].reshape(-1, 2) for k, n in enumerate(counts) if n]
+    if polys:
+        polys, points = torch.cat(polys, 0), torch.cat(points, 0)
+    else:
+        polys, points = torch.zeros(0, 32, dtype=torch.int32), torch.zeros(0, 2, dtype=torch.int32)
+    res = TL.TileStage(dev, args.num_bins).run(polys, points, row_start, rect, owner, page_size, P, tkw['edge'], tkw['drop_cut'])   # ONE device call
+    out = TL.tile_records(recs, res, rect, owner, len(imgs), names)
+    page_start = np.concatenate([[0], np.cumsum(res['page_count'])]).astype(np.int64)       # tiles are sorted by page: a page's rows are contiguous
+    page_polys = [res['page_polys'][int(page_start[p]):int(page_start[p + 1])] if len(out[p]) else None for p in range(len(imgs))]
+    return _finish_records(model, out, page_polys, page_hw, P, args, lexicon, lexicon_max_dist, lexicon_max_ratio, **skw)
 
 
 def _meta(t):

@@ -55,7 +55,8 @@ def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=
 def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, preprocessor=None, resizer=None, crop='box', ragged=False,
                        lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
                        grid=None, suppress=None, suppress_measure='iou', suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5,
-                       line_offset=0.5, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8):
+                       line_offset=0.5, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8, tiles=None, tile_size=None, tile_overlap=0.125,
+                       tile_edge=2, tile_cut='drop', page_bins=None):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -78,6 +79,10 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     blocks, block_gap_x, block_gap_y, block_depth: multi-column pages, as predict_images takes them (needs
     reading_order=True): the records gain `block` and come block by block BEFORE the crops, so `mgp_*` land on the reordered records;
     utils.reading.page_blocks(records, field='mgp_text') gives one string per block.
+    tiles=(nx, ny) or tile_size=, tile_overlap, tile_edge, tile_cut, page_bins: tiled pages, as predict_images takes them (DESIGN.md
+    section 20): the spotter reads every page as overlapping full-resolution tiles, the records come per page in PAGE pixels with
+    `tile`, `tile_rect` and `tile_cut`, and the crops are cut from the page images along those page-pixel polygons, at the page's
+    resolution.  The three defaults are choices that no data set has tested.
     Returns (results, preprocessor, resizer) so the cached tables can be reused."""
     if crop not in ('box', 'polygon'):
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
@@ -96,6 +101,10 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
         skw.update(reading_order=True, line_gap=line_gap, line_back=line_back, line_offset=line_offset)
         if blocks:
             skw.update(blocks=True, block_gap_x=block_gap_x, block_gap_y=block_gap_y, block_depth=block_depth)
+    if tiles is not None or tile_size is not None:
+        from ..utils import tiles as TL
+        TL.check_tile_args(tiles, tile_size, tile_overlap, tile_edge, tile_cut, page_bins, args.num_bins, args.infer_vie, windows)
+        skw.update(tiles=tiles, tile_size=tile_size, tile_overlap=tile_overlap, tile_edge=tile_edge, tile_cut=tile_cut, page_bins=page_bins)
     dev = next(omni_model.parameters()).device
     imgs = [torch.as_tensor(i).to(dev).contiguous() for i in images_u8]
     if lexicon is not None:

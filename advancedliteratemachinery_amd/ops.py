@@ -836,3 +836,42 @@ def reading_blocks(polys, tables, host_tables, n_groups, grid, lines, gap_x, gap
 def split_block_ints(ints, n, n_groups):
     """the int32 tensor of reading_blocks (on either side of the copy) -> (block, line, rank, n_blocks, levels)"""
     return tuple(ints[k * n:(k + 1) * n] for k in range(3)) + (ints[3 * n:3 * n + n_groups], ints[3 * n + n_groups:])
+
+
+def tile_remap(polys, points, tables, n_tiles, n_pages, nb, page_bins, edge, drop_cut=True, cap=None):
+    """omp_tile_remap (csrc/tiles.hip; utils/tiles.py: remap_cpu is the specification and pack_tables packs the table): polys int32
+    [N, 32] and points int32 [N, 2] in tile bins, tables device int32 [6 T + 1 + 2 pages] = row_start | tile_rect | tile_page |
+    page_size.  The tables go to the device as they are: a tile they describe wrongly is refused there (tile_count -1).
+    -> dict(page_polys int32 [cap, 32], page_points int32 [cap, 2]: the kept words in page bins, on the device; ints: ONE int32 tensor
+    [N + cap + 3 T + 1 + pages] = cut [N] | src_row [cap] | tile_count [T] | tile_dropped [T] | out_start [T + 1] | page_count [pages]
+    (split_tile_ints), so that a caller fetches everything in one copy).  cap defaults to N; the cut entries of words of no accepted
+    tile are -1, the src_row entries beyond the kept total -1."""
+    N, T, G = int(polys.shape[0]), int(n_tiles), int(n_pages)
+    if polys.dim() != 2 or polys.shape[1] != 32 or N < 1 or T < 1 or G < 1:
+        raise ValueError('polys must be [N, 32] with at least one word, one tile and one page')
+    for name, tt, numel in (('polys', polys, 32 * N), ('points', points, 2 * N), ('tables', tables, 6 * T + 1 + 2 * G)):
+        if not tt.is_cuda or tt.dtype != torch.int32 or not tt.is_contiguous() or tt.numel() != numel:
+            raise ValueError('%s must be a contiguous device int32 tensor with %d elements' % (name, numel))
+    cap = N if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError('cap must not be negative')
+    dev = polys.device
+    page_polys = torch.empty(max(cap, 1), 32, dtype=torch.int32, device=dev)
+    page_points = torch.empty(max(cap, 1), 2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(N, 34, dtype=torch.int32, device=dev)
+    ints = torch.full((N + max(cap, 1) + 3 * T + 1 + G,), -1, dtype=torch.int32, device=dev)
+    c0 = N + max(cap, 1)
+    rc = _lib.lib().omp_tile_remap(ptr(polys), ptr(points), N, ptr(tables), T, G, int(nb), int(page_bins), int(edge), 1 if drop_cut else 0,
+                                   ptr(scratch), ptr(ints[:N]), ptr(page_polys), ptr(page_points), ptr(ints[N:c0]), cap, ptr(ints[c0:c0 + T]),
+                                   ptr(ints[c0 + T:c0 + 2 * T]), ptr(ints[c0 + 2 * T:c0 + 3 * T + 1]), ptr(ints[c0 + 3 * T + 1:]), stream())
+    _lib.check(rc, 'omp_tile_remap')
+    if cap == 0:
+        ints = torch.cat([ints[:N], ints[c0:]])
+    return dict(page_polys=page_polys[:cap], page_points=page_points[:cap], ints=ints)
+
+
+def split_tile_ints(ints, n, n_tiles, n_pages, cap=None):
+    """the int32 tensor of tile_remap (on either side of the copy) -> (cut, src_row, tile_count, tile_dropped, out_start, page_count)"""
+    c0 = n + (n if cap is None else cap)
+    T = n_tiles
+    return ints[:n], ints[n:c0], ints[c0:c0 + T], ints[c0 + T:c0 + 2 * T], ints[c0 + 2 * T:c0 + 3 * T + 1], ints[c0 + 3 * T + 1:c0 + 3 * T + 1 + n_pages]

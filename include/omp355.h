@@ -724,6 +724,35 @@ int omp_reading_blocks(const int32_t* polys, int n, const int32_t* tables, const
                        int gap_y, int depth, const int32_t* line_in, const int32_t* line_pos_in, const int32_t* n_lines_in, int32_t* block,
                        int32_t* line, int32_t* rank, int32_t* n_blocks, int32_t* levels, omp_stream_t s);
 
+/* ---- tiled pages: the words of overlapping full-resolution tiles -> the words of their pages ----
+ * Neither reference project reads a page in tiles: both scale it to the model's input size.  utils/tiles.py::remap_cpu is the
+ * specification and every output integer equals it.  Integers only.
+ *   polys, points  int32 [n][32], [n][2]: the decoders' ids in TILE bins, every one CLAMPED on the device to [0, nb - 1]; 2 <= nb <= 4096
+ *   tables      device int32 [6 n_tiles + 1 + 2 n_pages] = row_start [n_tiles + 1] (words row_start[k] .. row_start[k + 1] - 1 are tile
+ *               k's) | tile_rect [n_tiles][4] (x0, y0, x1, y1 in page pixels, x1 / y1 exclusive) | tile_page [n_tiles] | page_size
+ *               [n_pages][2] (W, H; 1 .. 65535)
+ *   remapping   an x id c of a tile [x0, x1) on a page of width W -> min(P - 1, (2 (x0 nb + c (x1 - x0)) P + nb W) / (2 nb W)), P =
+ *               page_bins (2 .. 4096), in 64 bits; y with y0, y1 and H
+ *   cut bits    from the clamped ids of the word's 17 points: 1 x0 > 0 and min x <= edge; 2 y0 > 0 and min y <= edge; 4 x1 < W and
+ *               max x >= nb - 1 - edge; 8 y1 < H and max y >= nb - 1 - edge (0 <= edge <= 4096)
+ *   refusals    a tile whose row range is not 0 <= row_start[k] <= row_start[k + 1] <= n, whose page is outside the table or not 1 ..
+ *               65535 pixels a side, or whose rectangle is empty or leaves its page is REFUSED on the device: tile_count -1,
+ *               tile_dropped 0, and nothing else of it is written
+ * Outputs, all int32; everything but cut and scratch is written in full by the call:
+ *   scratch [n][34]  working space: the remapped row of every word of an accepted tile
+ *   cut [n]          the cut bits of the words of accepted tiles; the entries of other words are NOT written (ops.tile_remap
+ *                    initialises them to -1, which is what the specification gives them)
+ *   page_polys [cap][32], page_points [cap][2], src_row [cap]: the remapped rows and the word indices of the words with cut == 0 (of
+ *                    all words of accepted tiles when drop_cut is 0), in tile order and inside a tile in the decoder's order (a stable
+ *                    compaction); entries at or beyond cap are not written (out_start[n_tiles] still holds the full total)
+ *   tile_count, tile_dropped [n_tiles]: words kept / removed per tile;  out_start [n_tiles + 1]: exclusive prefix sum of the kept
+ *                    counts;  page_count [n_pages]: words kept per page (through tile_page)
+ * Three launches (flag, scan, copy); no allocation, no synchronisation. */
+int omp_tile_remap(const int32_t* polys, const int32_t* points, int n, const int32_t* tables, int n_tiles, int n_pages, int nb,
+                   int page_bins, int edge, int drop_cut, int32_t* scratch, int32_t* cut, int32_t* page_polys, int32_t* page_points,
+                   int32_t* src_row, int cap, int32_t* tile_count, int32_t* tile_dropped, int32_t* out_start, int32_t* page_count,
+                   omp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
