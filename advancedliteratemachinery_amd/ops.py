@@ -768,6 +768,45 @@ def split_overlap_ints(ints, n):
     return ints[:4 * n].reshape(n, 4), ints[4 * n:5 * n], ints[5 * n:6 * n], ints[6 * n:]
 
 
+def spotting_match(inter, inter_start, group_start, n_gt, gt_dc, text, level, n_thr, t_iou, t_dc, report=-1, out=None):
+    """omp_spotting_match (csrc/score.hip; utils/scoring.py holds the specification): inter int32, polygon_overlap's dense matrices (None
+    when there is no polygon), inter_start int64 [G + 1], group_start int32 [G + 1], n_gt int32 [G], gt_dc / text / level int32 [n] with
+    n = the number of polygons, ground truth first inside every group; t_iou, t_dc in permille; report -1 or a threshold index.
+    -> ONE int32 tensor [4 G n_thr + 2 n] = counts [G, n_thr, 4] | det_gt [n] | gt_det [n] (split_match_ints), so that a caller fetches
+    everything in one copy."""
+    G, n = int(group_start.numel()) - 1, int(level.numel())
+    if G < 1:
+        raise ValueError('group_start must hold at least one group')
+    for name, tt, dtype, numel in (('inter', inter, torch.int32, None), ('inter_start', inter_start, torch.int64, G + 1),
+                                   ('group_start', group_start, torch.int32, G + 1), ('n_gt', n_gt, torch.int32, G), ('gt_dc', gt_dc, torch.int32, n),
+                                   ('text', text, torch.int32, n), ('level', level, torch.int32, n)):
+        if tt is None:
+            if name == 'inter' and n == 0:
+                continue
+            raise ValueError('%s is missing' % name)
+        if not tt.is_cuda or tt.dtype != dtype or not tt.is_contiguous() or (numel is not None and tt.numel() != numel):
+            raise ValueError('%s must be a contiguous device %s tensor%s' % (name, dtype, '' if numel is None else ' with %d elements' % numel))
+    n_thr = int(n_thr)
+    size = 4 * G * max(n_thr, 0) + 2 * n
+    dev = group_start.device
+    if out is None:
+        out = torch.empty(max(size, 1), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != max(size, 1) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor with %d elements' % max(size, 1))
+    c = 4 * G * max(n_thr, 0)
+    rc = _lib.lib().omp_spotting_match(ptr(inter), ptr(inter_start), ptr(group_start), ptr(n_gt), ptr(gt_dc) if n else None, ptr(text) if n else None,
+                                       ptr(level) if n else None, n, G, n_thr, int(t_iou), int(t_dc), int(report), ptr(out),
+                                       ptr(out[c:c + n]) if n else None, ptr(out[c + n:c + 2 * n]) if n else None, stream())
+    _lib.check(rc, 'omp_spotting_match')
+    return out[:size]
+
+
+def split_match_ints(ints, n, n_groups, n_thr):
+    """the int32 tensor of spotting_match (on either side of the copy) -> (counts [G, n_thr, 4], det_gt [n], gt_det [n])"""
+    c = 4 * n_groups * n_thr
+    return ints[:c].reshape(n_groups, n_thr, 4), ints[c:c + n], ints[c + n:c + 2 * n]
+
+
 def _reading_tables(polys, tables, host_tables, n_groups):
     N, G = int(polys.shape[0]), int(n_groups)
     for name, tt, numel in (('polys', polys, 32 * N), ('tables', tables, 3 * G + 1)):

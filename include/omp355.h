@@ -677,6 +677,37 @@ int omp_polygon_overlap(const int32_t* polys, int n, const int32_t* group_start,
 int omp_polygon_keep(const uint64_t* mask, const int64_t* mask_start, int64_t mask_words, const int32_t* group_start, int n_groups, int n,
                      const int32_t* order, int32_t* owner, int32_t* kept, omp_stream_t s);
 
+/* ---- scoring: spotting results against ground truth under the IoU protocol ----
+ * Neither reference project scores its results: engine/val.py writes a results JSON and stops.  utils/scoring.py holds the
+ * specification (match_cpu, match_pages_cpu); this entry point equals it on every output integer.  Protocol: the polygons of image g
+ * are ordered ground truth first (n_gt[g] of them), then detections; inter is omp_polygon_overlap's dense matrix of the group, so
+ * area[p] = inter[p][p].  Detection d is ACTIVE at threshold index k iff level[d] > k.  Per (image, k):
+ *   don't-care  an active detection d is don't-care when some ground-truth word i has gt_dc[i] != 0, inter[i][d] > 0 and
+ *               1000 inter[i][d] >= t_dc area[d]
+ *   matching    the ground-truth words i with gt_dc[i] == 0 are visited in index order; each takes the lowest-index detection d that
+ *               is active, not don't-care, not yet taken, with inter[i][d] > 0 and 1000 inter[i][d] >= t_iou (area[i] + area[d] -
+ *               inter[i][d]); 64-bit products.  A detection of area 0 never matches and is never don't-care.
+ *   counts [n_groups][n_thr][4] = care ground truth, care detections (active and not don't-care), matched, matched with
+ *               text[i] == text[d]
+ * Inputs:
+ *   inter        int32, group g's n_g x n_g matrix from inter_start[g] (int64 [n_groups + 1]; inter_start[n_groups] is the number of
+ *                entries, which the caller guarantees the buffer holds)
+ *   group_start  int32 [n_groups + 1], n_gt int32 [n_groups]; gt_dc, text, level int32 [n], indexed like the polygons (gt_dc is
+ *                read at ground-truth rows only, level at detection rows only)
+ *   n_thr 1 .. 64, t_iou and t_dc in permille 1 .. 1000, report -1 or a threshold index
+ * Outputs: counts, written in full.  det_gt / gt_det int32 [n] (both or neither; needed when report >= 0), written in full: for
+ *   k == report det_gt[d] = the matched ground-truth index inside the image, -1 care and unmatched, -2 don't-care, -3 inactive, at
+ *   the detections' rows, and gt_det[i] = the matched detection's index among the image's detections, -1 unmatched, -2 don't-care, at
+ *   the ground truth's rows; every other row, and every row when report is -1, holds -4.
+ * OMP_ERR_INVALID, nothing launched: a null pointer (inter, gt_dc, text and level may be null when n is 0), n_groups < 1, n_thr, t_iou,
+ *   t_dc or report outside their ranges.  The tables live in device memory, so what only they show is REFUSED on the device, as
+ *   omp_polygon_keep does: an image of more than 8192 polygons, n_gt[g] outside 0 .. n_g, or a matrix outside the inter table gets
+ *   counts of -1 (all n_thr x 4 of them) and -4 in its assignment rows, and reads nothing of inter.
+ * One launch, a workgroup per (image, threshold); no allocation, no synchronisation. */
+int omp_spotting_match(const int32_t* inter, const int64_t* inter_start, const int32_t* group_start, const int32_t* n_gt,
+                       const int32_t* gt_dc, const int32_t* text, const int32_t* level, int n, int n_groups, int n_thr, int t_iou,
+                       int t_dc, int report, int32_t* counts, int32_t* det_gt, int32_t* gt_det, omp_stream_t s);
+
 /* ---- reading order: words -> text lines -> the order a reader takes them in ----
  * Neither reference project orders its words: they leave the engine in decoder order.  utils/reading.py holds the specification
  * (features_cpu, links_cpu, lines_cpu); every output integer equals it.  Integers only.
