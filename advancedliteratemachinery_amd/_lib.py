@@ -144,6 +144,8 @@ _SIGS = {
     'omp_polygon_rectify': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
     'omp_resize_crops': (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'omp_lexicon_nearest': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'omp_logprob_costs': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'omp_lexicon_posterior': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'omp_window_points': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int] + [c_void_p] * 5),
     'omp_polygon_overlap': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p]),
     'omp_polygon_keep': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int] + [c_void_p] * 4),

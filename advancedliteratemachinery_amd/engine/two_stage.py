@@ -33,21 +33,30 @@ def polygon_box(polys, width, height):
 
 
 @torch.no_grad()
-def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=None):
+def recognize_crops(mgp_model, images_u8, boxes, resizer=None, chunk=512, polys=None, keep_logits=False):
     """boxes: (image index, x0, y0, x1, y1).  -> list of MGPSTR.recognize results (one dict per box).
     polys: (image index, 16 x 2 points) per crop instead of boxes (boxes is then ignored): the crops are rectified along
-    their polygons (utils/word_crops.py: PolygonCropper), and `resizer` is a PolygonCropper."""
+    their polygons (utils/word_crops.py: PolygonCropper), and `resizer` is a PolygonCropper.
+    keep_logits=True: -> (results, resizer, logits): the character head's fp32 logits of all crops [n, 27, 38], kept on the
+    device across the chunks (None without crops)."""
     crops = boxes if polys is None else polys
     if not crops:
-        return [], resizer
+        return ([], resizer, None) if keep_logits else ([], resizer)
     dev = images_u8[0].device
     if resizer is None:
         c = mgp_model.cfg
         resizer = (CropResizer if polys is None else PolygonCropper)(dev, c['img'][0], c['img'][1])
-    out = []
+    out, kept = [], []
     for i in range(0, len(crops), chunk):
         batch = resizer(images_u8, crops[i:i + chunk])
-        out.extend(mgp_model.recognize(batch))
+        if keep_logits:
+            res, logits = mgp_model.recognize(batch, char_logits=True)
+            out.extend(res)
+            kept.append(logits)
+        else:
+            out.extend(mgp_model.recognize(batch))
+    if keep_logits:
+        return out, resizer, kept[0] if len(kept) == 1 else torch.cat(kept, 0)
     return out, resizer
 
 
@@ -56,7 +65,7 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
                        lexicon=None, lexicon_max_dist=None, lexicon_max_ratio=None, windows=None, char_windows=None, clip_windows=False,
                        grid=None, suppress=None, suppress_measure='iou', suppress_order='first', reading_order=False, line_gap=2.0, line_back=0.5,
                        line_offset=0.5, blocks=False, block_gap_x=1.0, block_gap_y=1.5, block_depth=8, tiles=None, tile_size=None, tile_overlap=0.125,
-                       tile_edge=2, tile_cut='drop', page_bins=None):
+                       tile_edge=2, tile_cut='drop', page_bins=None, lexicon_mode='edit', lexicon_min_prob=None, lexicon_min_margin=None):
     """uint8 RGB [H, W, 3] images -> per image the OmniParser records, each extended by the recogniser's reading of its
     crop: `box` (x0, y0, x1, y1), `mgp_text` (character-head string up to its EOS), `mgp_conf` (char, bpe, wp),
     `mgp_choice` (0 char / 1 bpe / 2 wp / -1 none: the most confident head, test_final.py:172-236) and the raw ids of
@@ -68,6 +77,14 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
     lexicon_max_ratio: records gain `lex`, `lex_index`, `lex_dist` from `rec` (predict_images) and `mgp_lex`, `mgp_lex_index`,
     `mgp_lex_dist` from `mgp_text`; a raw list is encoded with args.chars for the one and MGP-STR's character set for the
     other, a matcher serves both with its own alphabet.  One device call per source string for all words of all images.
+    lexicon_mode='posterior', lexicon_min_prob, lexicon_min_margin: posterior lexicon decoding (DESIGN.md section 22;
+    utils/lexicon_post.py): `mgp_lex` becomes the lexicon word of greatest probability under MGP-STR's character head instead
+    of the nearest word of the greedy string.  The crops' character logits stay on the device, ONE posterior call scores all words
+    of all images (per-image lists through ranges), and the records gain `mgp_lex`, `mgp_lex_index`, `mgp_lex_logp` (nats),
+    `mgp_lex_second` ((index, logp) of the runner-up or None) and `mgp_lex_gap` (nats below the greedy path; may be negative) --
+    no `mgp_lex_dist`.  A word is rejected (`mgp_lex` None) below lexicon_min_prob or when the runner-up is closer than
+    lexicon_min_margin nats.  `lex*` from `rec` stays edit-distance under lexicon_max_dist / lexicon_max_ratio: OmniParser's
+    recogniser is autoregressive.  'edit' (the default) is the behaviour described above.
     windows, char_windows, clip_windows, grid=(nx, ny): window prompts, as predict_images takes them: the
     spotter reads every window of every image in one engine call, the records gain `window` and `window_bins`, and the recogniser
     reads the crops of all windows' words exactly as it reads the plain call's.
@@ -88,6 +105,17 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
         raise ValueError("crop must be 'box' or 'polygon', got %r" % (crop,))
     if lexicon is not None and args.infer_vie:
         raise ValueError('lexicon= needs text-spotting records; with args.infer_vie the engine returns entity tuples')
+    if lexicon_mode not in ('edit', 'posterior'):
+        raise ValueError("lexicon_mode must be 'edit' or 'posterior', got %r" % (lexicon_mode,))
+    if lexicon_mode != 'posterior' and (lexicon_min_prob is not None or lexicon_min_margin is not None):
+        raise ValueError("lexicon_min_prob / lexicon_min_margin belong to lexicon_mode='posterior'")
+    if lexicon_mode == 'posterior':
+        if args.infer_vie:
+            raise ValueError("lexicon_mode='posterior' needs text-spotting records; with args.infer_vie the engine returns entity tuples")
+        if lexicon is None:
+            raise ValueError("lexicon_mode='posterior' needs lexicon=")
+        from ..utils import lexicon_post as LP
+        LP.check_post_args(lexicon_min_prob, lexicon_min_margin)
     skw = {}
     if suppress is not None:
         from ..utils import overlap as OV
@@ -124,12 +152,18 @@ def spot_and_recognize(omni_model, mgp_model, images_u8, args, file_names=None, 
                 r['crop'], r['strip'] = 'polygon', polygon_strip_size(r['polys'])
                 polys.append((b, r['polys']))
             owner.append(r)
-    reads, resizer = recognize_crops(mgp_model, imgs, boxes, resizer, polys=polys if crop == 'polygon' else None)
+    if lexicon_mode == 'posterior':
+        reads, resizer, char_logits = recognize_crops(mgp_model, imgs, boxes, resizer, polys=polys if crop == 'polygon' else None, keep_logits=True)
+    else:
+        reads, resizer = recognize_crops(mgp_model, imgs, boxes, resizer, polys=polys if crop == 'polygon' else None)
     for r, m in zip(owner, reads):
         r['mgp_text'], r['mgp_conf'], r['mgp_choice'] = m['char_text'], m['conf'], m['choice']
         r['mgp_ids'] = dict(char=m['char_ids'], bpe=m['bpe_ids'], wp=m['wp_ids'])
     if lexicon is not None:
         from ..model.mgp_str import CHARACTER
         matcher = LX.resolve_lexicon(lexicon, len(records), dev, CHARACTER)
-        LX.annotate_records(records, matcher, 'mgp_text', 'mgp_lex', lexicon_max_dist, lexicon_max_ratio)
+        if lexicon_mode == 'posterior':
+            LP.annotate_posterior(records, matcher, char_logits, 'mgp_lex', lexicon_min_prob, lexicon_min_margin)
+        else:
+            LX.annotate_records(records, matcher, 'mgp_text', 'mgp_lex', lexicon_max_dist, lexicon_max_ratio)
     return records, preprocessor, resizer

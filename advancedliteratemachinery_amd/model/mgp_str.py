@@ -307,27 +307,50 @@ class MGPSTR(nn.Module):
         return [attens] + outs if is_eval else outs
 
     @torch.no_grad()
-    def greedy(self, input):
+    def greedy(self, input, char_logits=False):
         """The device part of recognition (test_final.py:145-170): -> [(ids int32 [B, S], prob fp32 [B, S])] for char / bpe / wp.  The wide heads
-        (BPE 50 257, WordPiece 30 522 classes) decode from the head product's per-tile row statistics -- no logits tensor (greedy_fused)."""
+        (BPE 50 257, WordPiece 30 522 classes) decode from the head product's per-tile row statistics -- no logits tensor (greedy_fused).
+        char_logits=True: -> (that list, the character head's fp32 logits [B, S, classes] on the device).  The character head is narrower than
+        GREEDY_FUSED_MIN_CLASSES, so its logits exist on the default path too: the same launches, the tensor is kept instead of dropped."""
         if self.training:
             raise NotImplementedError('training is out of scope for the MI355X inference engine')
         if not input.is_cuda:
             raise RuntimeError('MGPSTR runs on MI355X only: pass device tensors; there is no CPU fallback')
         with torch.cuda.device(input.device):
             x, B, T = self.encode(input)
+            if char_logits:
+                logits = self._a3_head(x, B, T, GRANULARITIES[0], False)[1]
+                out = [ops.row_argmax_prob_2d(logits.view(B * logits.shape[1], -1), B, logits.shape[1])]
+                out += [self._a3_head(x, B, T, name, False, greedy=True)[1] for name in GRANULARITIES[1:]]
+                return out, logits
             return [self._a3_head(x, B, T, name, False, greedy=True)[1] for name in GRANULARITIES]
 
     # result decoding (test_final.py:145-240) ---------------------------------------------------------
     @torch.no_grad()
-    def recognize(self, input, bpe_vocab=None, wp_vocab=None):
+    def recognize(self, input, bpe_vocab=None, wp_vocab=None, lexicon=None, lexicon_ranges=None, lexicon_min_prob=None, lexicon_min_margin=None,
+                  char_logits=False):
         """-> list of dicts per image: greedy ids of the three granularities (position 0 dropped), their confidences,
         the fused choice (0 char / 1 bpe / 2 wp / -1 none) and the character-level string.  bpe_vocab / wp_vocab: paths of a LOCAL
         GPT-2 `vocab.json` / BERT `vocab.txt` (or utils.mgp_tokens.BpeVocab / WordPieceVocab objects): the records then also
         carry `bpe_text`, `wp_text` and the fused `text` of test_final.py:196-236 (the reference fetches both tokenizers from
-        the hub, utils.py:23-24; without the files the engine stops at ids + confidences)."""
+        the hub, utils.py:23-24; without the files the engine stops at ids + confidences).
+        lexicon (a utils.lexicon.LexiconMatcher), lexicon_ranges ((lo, hi) per image, default the whole lexicon), lexicon_min_prob,
+        lexicon_min_margin: posterior lexicon decoding (utils/lexicon_post.py) -- the results gain `lex` (the
+        lexicon word of greatest probability under the character head, None when there is none or it is rejected), `lex_index`,
+        `lex_logp` (nats), `lex_second` ((index, logp) of the runner-up or None) and `lex_gap` (nats below the greedy path; may be
+        negative).  char_logits=True: -> (results, the character head's fp32 logits on the device)."""
+        if lexicon is None and (lexicon_ranges is not None or lexicon_min_prob is not None or lexicon_min_margin is not None):
+            raise ValueError('lexicon_ranges / lexicon_min_prob / lexicon_min_margin need lexicon=')
+        if lexicon is not None or char_logits:
+            if lexicon is not None:
+                from ..utils import lexicon_post as LP
+                LP.check_post_args(lexicon_min_prob, lexicon_min_margin)
+                post = LP.posterior_of(lexicon)
+            heads, logits = self.greedy(input, char_logits=True)
+        else:
+            heads, logits = self.greedy(input), None
         ids, probs = [], []
-        for i, p in self.greedy(input):
+        for i, p in heads:
             ids.append(i[:, 1:].cpu())
             probs.append(p[:, 1:].cpu())
         res = decode_ids(ids, probs)
@@ -336,7 +359,10 @@ class MGPSTR(nn.Module):
             bpe = MT.BpeVocab(bpe_vocab) if isinstance(bpe_vocab, str) else bpe_vocab
             wp = MT.WordPieceVocab(wp_vocab) if isinstance(wp_vocab, str) else wp_vocab
             MT.decode_strings(res, bpe, wp)
-        return res
+        if lexicon is not None:
+            for r, d in zip(res, post(logits, ranges=lexicon_ranges, min_prob=lexicon_min_prob, min_margin=lexicon_min_margin)):
+                r.update(LP.result_keys(d, 'lex'))
+        return (res, logits) if char_logits else res
 
 
 def decode_ids(ids, probs):

@@ -680,6 +680,57 @@ def lexicon_nearest(q_codes, q_len, q_lo, q_hi, pool, pool_bytes, offsets, L, be
     return best
 
 
+def logprob_costs(logits, costs=None, greedy=None, n=None):
+    """omp_logprob_costs (csrc/lexicon_post.hip; utils/lexicon_post.py: costs_cpu / greedy_cpu are the specification): the character
+    head's logits fp32 [N, 27, 38] -> (costs int32 [N, 26, 38], greedy int32 [N, 2])."""
+    if logits is not None:
+        _c(logits, 'logits')
+        if logits.dtype != torch.float32 or logits.dim() != 3 or tuple(logits.shape[1:]) != (27, 38):
+            raise ValueError('logits must be fp32 [N, 27, 38], got %s %s' % (logits.dtype, tuple(logits.shape)))
+    N = int(logits.shape[0]) if n is None else int(n)
+    if costs is None:
+        costs = torch.empty((max(N, 0), 26, 38), dtype=torch.int32, device=logits.device)
+    if greedy is None:
+        greedy = torch.empty((max(N, 0), 2), dtype=torch.int32, device=logits.device)
+    for name, t, numel in (('costs', costs, N * 26 * 38), ('greedy', greedy, N * 2)):
+        if t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous int32 tensor with at least %d elements' % (name, numel))
+    rc = _lib.lib().omp_logprob_costs(ptr(logits), N, ptr(costs), ptr(greedy), stream())
+    _lib.check(rc, 'omp_logprob_costs')
+    return costs, greedy
+
+
+LEXICON_POST_WORK_SLICES = 4096   # omp_lexicon_posterior: work holds 2 * (n + 4096) uint64 (include/omp355.h)
+
+
+def lexicon_posterior(costs, q_lo, q_hi, pool, pool_bytes, offsets, L, class_table, range_hint=0, best=None, work=None, n=None):
+    """omp_lexicon_posterior (csrc/lexicon_post.hip; utils/lexicon_post.py: score_cpu is the specification): costs int32 [N, 26, 38],
+    q_lo / q_hi int32 [N] (both None: the whole lexicon), pool uint8 with pool_bytes valid bytes, offsets int32 [L + 1], class_table
+    uint8 [256] -> best int64 [N, 2] holding the uint64 keys (score << 32) | idx of the best word and of the runner-up, all ones =
+    none.  work: int64 scratch of at least 2 * (N + 4096) elements (allocated here when None)."""
+    N = int(costs.shape[0]) if n is None else int(n)
+    for name, t, dtype, numel in (('costs', costs, torch.int32, N * 26 * 38), ('q_lo', q_lo, torch.int32, N), ('q_hi', q_hi, torch.int32, N),
+                                  ('pool', pool, torch.uint8, pool_bytes), ('offsets', offsets, torch.int32, L + 1),
+                                  ('class_table', class_table, torch.uint8, 256)):
+        if t is None:
+            continue
+        _c(t, name)
+        if t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be %s with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if best is None:
+        best = torch.empty((max(N, 0), 2), dtype=torch.int64, device=costs.device)
+    elif best.dtype != torch.int64 or best.numel() < 2 * N or not best.is_contiguous():
+        raise ValueError('best must be a contiguous int64 tensor with at least %d elements' % (2 * N))
+    if work is None:
+        work = torch.empty(2 * (max(N, 0) + LEXICON_POST_WORK_SLICES), dtype=torch.int64, device=best.device)
+    elif work.dtype != torch.int64 or work.numel() < 2 * (N + LEXICON_POST_WORK_SLICES) or not work.is_contiguous():
+        raise ValueError('work must be a contiguous int64 tensor with at least %d elements' % (2 * (N + LEXICON_POST_WORK_SLICES)))
+    rc = _lib.lib().omp_lexicon_posterior(ptr(costs), N, ptr(q_lo), ptr(q_hi), ptr(pool), pool_bytes, ptr(offsets), L, ptr(class_table),
+                                          int(range_hint), ptr(best), ptr(work), stream())
+    _lib.check(rc, 'omp_lexicon_posterior')
+    return best
+
+
 def window_points(seq, finished, lengths, row_image, n_images, n_prompt, sampled, clip=False, cap=None):
     """omp_window_points (csrc/window_points.hip; utils/windows.py: gather_points_cpu is the specification): the buffers of a finished
     point phase -- seq int32 [rows, seq_ld], finished / lengths int32 [rows] -- and the row -> image table

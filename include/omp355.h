@@ -618,6 +618,40 @@ int omp_lexicon_nearest(const uint8_t* q_codes, const int32_t* q_len, const int3
                         const uint8_t* pool, int64_t pool_bytes, const int32_t* offsets, int L, int range_hint,
                         uint64_t* best, omp_stream_t s);
 
+/* ---- posterior lexicon decoding: the lexicon word MGP-STR's character head finds most likely ----
+ * The character head is non-autoregressive, so P(word) = prod_i p_i(word[i]) * p_len([s]) is the exact probability that
+ * the reference's decoding rule (OCR/MGP-STR/test_final.py:172-181) yields the word.  utils/lexicon_post.py holds the
+ * specification (costs_cpu, greedy_cpu, score_cpu and the pure-Python score_py).  Floats end at the costs:
+ *   logits   float [n][27][38], contiguous: the character head's logits; position 0 is dropped, as recognize does
+ *   costs    int32 [n][26][38], written by this call: clip(floor(-log_softmax * 1024 + 0.5), 0, 2^20 - 1), one unit =
+ *            1/1024 nat; max, sum of exp and log in fp32, so a cost may differ from costs_cpu (float64) by one unit at a
+ *            rounding boundary and by no more
+ *   greedy   int32 [n][2], written by this call from the quantised costs: (sum of the per-position least costs through the
+ *            first position whose least class is 1 = [s], that position); (26 terms, 26) without one.  Lowest class among equals.
+ * One launch of n workgroups; no allocation, no synchronisation.  n <= 0 or a null pointer: OMP_ERR_INVALID, nothing launched. */
+int omp_logprob_costs(const float* logits, int n, int32_t* costs, int32_t* greedy, omp_stream_t s);
+/* The search.  score(q, w) = sum_{i < len} costs[q][i][class_table[w[i]]] + costs[q][len][1]; integers only, every output
+ * equals score_cpu.
+ *   costs    int32 [n][26][38] as above (any int32 in [0, 2^20) keeps 26 terms far below 2^31)
+ *   q_lo, q_hi  int32 [n] each, or both NULL: query q searches the lexicon indices [q_lo[q], q_hi[q]), CLAMPED on the device
+ *            to [0, L]; an inverted range is empty; NULL = the whole lexicon
+ *   pool, pool_bytes, offsets, L  the lexicon as omp_lexicon_nearest takes it.  Word i is pool[s, e) with
+ *            s = clip(offsets[i], 0, pool_bytes), e = clip(offsets[i + 1], s, pool_bytes): a falling or overlong table never
+ *            makes the kernel read outside pool[0 .. pool_bytes).  A word longer than 25 codes is SKIPPED, not truncated
+ *   class_table  uint8 [256]: lexicon code -> class 2..37; any other entry (255 by convention) = unscorable: a word that
+ *            holds such a code is skipped
+ *   range_hint  the longest range of the call if the caller knows it, else 0: sizes the grid only, never the result
+ *   best     uint64 [n][2], written by this call (the caller initialises nothing): [q][0] the least key (score << 32) | index
+ *            of the range, the lowest index among equals; [q][1] the least key among the OTHER indices (the runner-up; a
+ *            duplicate spelling at another index counts); all ones where there is none
+ *   work     uint64 [2 * (n + 4096)], caller-owned scratch: the per-slice pairs between the two launches
+ * Two launches (search, merge) whatever n and L; the result does not depend on scheduling; no allocation, no synchronisation,
+ * no atomics.  A null pointer, q_lo without q_hi, n <= 0, L <= 0, pool_bytes < 0 or range_hint < 0: OMP_ERR_INVALID, nothing
+ * launched and nothing written. */
+int omp_lexicon_posterior(const int32_t* costs, int n, const int32_t* q_lo, const int32_t* q_hi, const uint8_t* pool,
+                          int64_t pool_bytes, const int32_t* offsets, int L, const uint8_t* class_table, int range_hint,
+                          uint64_t* best, uint64_t* work, omp_stream_t s);
+
 /* ---- window prompts: the points of a finished point phase, compacted on the device ----
  * The point decoder's prompt holds a spatial window; an engine call may run several windows per image as rows of ONE point
  * phase (the reference's forward takes any such prompt, model/transformer.py:102-141; its training draws them,
