@@ -3,6 +3,10 @@ score thresholds (utils/scoring.py holds the protocol and 
 
     score_records      the records any entry point returns + ground-truth words -> counts and metrics, ONE device flow per call
     evaluate_spotting  images + ground truth -> predict_images / spot_and_recognize in calls of `batch`, scored as they come
+    score_page_text    the records of every image as ONE string against the page's ground-truth text: the normalised edit distance, which
+                       depends on the order of the records (utils/page_text.py holds the specification)
+    sweep_reading      the same records re-ordered under every candidate setting of the reading stage, all scored in ONE device call
+    evaluate_reading   images + ground-truth texts -> engine calls of `batch`, then score_page_text or sweep_reading
 
 Agreement with the official ICDAR / Total-Text evaluation scripts has not been checked (they are not part of this project)."""
 import inspect
@@ -142,5 +146,148 @@ def evaluate_spotting(model, images_u8, ground_truth, args, batch=8, mgp=None, b
             matches.extend(part['matches'])
     out = summarise(np.concatenate(counts + [np.zeros((0, th.size, 4), np.int32)]), th)
     out['matches'] = matches if skw.get('report') is not None else None
+    out['records'] = records
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# page text: the normalised edit distance of whole pages
+# ---------------------------------------------------------------------------------------------
+READING_KEYS = ('line_gap', 'line_back', 'line_offset', 'blocks', 'block_gap_x', 'block_gap_y', 'block_depth')
+
+
+def _check_page_records(records, gt_texts, text_key, what):
+    if text_key not in TEXT_KEYS:
+        raise ValueError('text_key must be one of %s, got %r' % (sorted(TEXT_KEYS), text_key))
+    if len(records) != len(gt_texts):
+        raise ValueError('records and gt_texts are per image: got %d and %d' % (len(records), len(gt_texts)))
+    for b, recs in enumerate(records):
+        for r in recs:
+            if not isinstance(r, dict) or 'polys' not in r:
+                raise ValueError('image %d: %s needs text-spotting records (dicts with `polys`)' % (b, what))
+
+
+def _gt_string(gt, strip, normalise):
+    from ..utils import page_text as PT
+    return PT.page_string(gt, 'text', strip, normalise)
+
+
+def _page_summary(dist, a_len, b_len):
+    from ..utils import page_text as PT
+    s = PT.page_scores(dist, a_len, b_len)
+    return dict(dist=np.asarray(dist, dtype=np.int32), len_pred=np.asarray(a_len, dtype=np.int32), len_gt=np.asarray(b_len, dtype=np.int32),
+                score=s['score'], mean=s['mean'], micro=s['micro'])
+
+
+def score_page_text(records, gt_texts, text_key='rec', strip=' \n', normalise=str.casefold, scorer=None, device=None):
+    """records: per image the list of record dicts any entry point returns, IN THE ORDER IT RETURNED THEM (the text under `text_key`,
+    with the fallbacks of score_records).  gt_texts: per image the page's text -- one string, or the list of its words in reading
+    order (strings, or dicts with `text`); whether the annotation's order is the reading order is the caller's responsibility.
+    Every image becomes one prediction string and one ground-truth string (utils.page_text.page_string: concatenated, the characters
+    of `strip` removed, `normalise` applied or None) and is scored by the reference's normalised edit distance.
+    scorer: a utils.page_text.PageTextScorer, or anything with its `run` (HostPageScorer: the specification); default: one on `device`
+    (default 'cuda').  All images go through the scorer in one call.
+    -> dict(dist int32 [G] = the Levenshtein distance per image, len_pred, len_gt int32 [G], score float64 [G] = 1 - dist / max(len_pred,
+    len_gt) (1.0 for two empty strings), mean = the average of score (the reference's figure), micro = 1 - sum(dist) / sum(max))."""
+    from ..utils import page_text as PT
+    _check_page_records(records, gt_texts, text_key, 'score_page_text')
+    pred = [PT.page_string(recs, text_key, strip, normalise) for recs in records]
+    truth = [_gt_string(gt, strip, normalise) for gt in gt_texts]
+    pool, a_off, a_len, b_off, b_len, sigma = PT.encode_pairs(pred, truth)
+    if scorer is None:
+        scorer = PT.PageTextScorer('cuda' if device is None else device)
+    dist = scorer.run(pool, a_off, a_len, b_off, b_len, sigma)
+    return _page_summary(dist, a_len, b_len)
+
+
+def sweep_reading(records, sizes, bins, gt_texts, settings, text_key='rec', strip=' \n', normalise=str.casefold, reader=None, scorer=None,
+                  device=None):
+    """The reading stage's knobs against ground-truth page texts, without running the model again.  records, gt_texts: as
+    score_page_text; sizes: (h, w) per image; settings: a list whose entries are None ("as given, not re-ordered") or dicts of
+    utils.reading.order_records' keywords line_gap, line_back, line_offset, blocks, block_gap_x, block_gap_y, block_depth.
+    Every setting re-orders COPIES of the records with order_records (one reading call per setting: `reader`, a
+    utils.reading.ReadingOrder or anything with its __call__; default: one on `device`).  The polygons are
+    utils.scoring.quantise(r['polys'], size, bins): the grid of DESIGN.md section 21, computed from the records' pixels, which can sit
+    one bin below the ids the polygon decoder itself produced -- no private engine state is needed.
+    All images x settings are scored in ONE scorer.run; a page's ground truth is stored once and shared by its settings.
+    -> dict(settings = per setting score_page_text's result, best = the index of the highest mean, ties to the lowest)."""
+    import torch
+
+    from ..utils import page_text as PT
+    from ..utils import reading as RD
+    _check_page_records(records, gt_texts, text_key, 'sweep_reading')
+    if len(sizes) != len(records):
+        raise ValueError('records and sizes are per image: got %d and %d' % (len(records), len(sizes)))
+    settings = list(settings)
+    if not settings:
+        raise ValueError('settings must hold at least one entry')
+    for k, st in enumerate(settings):
+        if st is not None and (not isinstance(st, dict) or any(key not in READING_KEYS for key in st)):
+            raise ValueError('setting %d must be None or a dict with keys among %s, got %r' % (k, list(READING_KEYS), st))
+    G = len(records)
+    polys = None
+    pred = []
+    for st in settings:
+        if st is None:
+            ordered = records
+        else:
+            if polys is None:
+                polys = [torch.from_numpy(SC.quantise([r['polys'] for r in recs], size, bins)) for recs, size in zip(records, sizes)]
+            copies = [[dict(r) for r in recs] for recs in records]
+            ordered = RD.order_records(copies, polys, sizes, int(bins), reader=reader, device='cuda' if device is None and reader is None else device, **st)
+        pred += [PT.page_string(recs, text_key, strip, normalise) for recs in ordered]
+    truth = [_gt_string(gt, strip, normalise) for gt in gt_texts]
+    pool, a_off, a_len, b_off, b_len, sigma = PT.encode_pairs(pred, truth * len(settings))
+    if scorer is None:
+        scorer = PT.PageTextScorer('cuda' if device is None else device)
+    dist = scorer.run(pool, a_off, a_len, b_off, b_len, sigma)
+    out = [_page_summary(dist[k * G:(k + 1) * G], a_len[k * G:(k + 1) * G], b_len[k * G:(k + 1) * G]) for k in range(len(settings))]
+    means = [s['mean'] for s in out]
+    return dict(settings=out, best=means.index(max(means)))
+
+
+_PAGE_ARGS = ('text_key', 'strip', 'normalise', 'scorer', 'device', 'reader')
+
+
+def evaluate_reading(model, images_u8, gt_texts, args, batch=8, mgp=None, settings=None, **kw):
+    """images_u8: uint8 RGB [H, W, 3] arrays / tensors; gt_texts: per image the page's text (score_page_text).  The images go through
+    predict_images -- spot_and_recognize(model, mgp, ...) when a recogniser `mgp` is given -- in calls of `batch`; text_key, strip,
+    normalise, scorer, device and reader go to the scoring, `bins` (default args.num_bins) is sweep_reading's grid, every other
+    keyword (ragged, windows / grid, suppress, reading_order, blocks, lexicon, tiles, ...) to the engine call.  The records are
+    collected and the distances are put together at the end: score_page_text over all images, or, with `settings`, sweep_reading.
+    -> that function's result, plus `records`: the records per image.  KIE is refused: entity tuples are not words."""
+    if args.infer_vie:
+        raise ValueError('evaluate_reading scores text-spotting records; with args.infer_vie the engine returns entity tuples')
+    if len(images_u8) != len(gt_texts):
+        raise ValueError('%d images for %d ground-truth texts' % (len(images_u8), len(gt_texts)))
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError('batch must be at least 1, got %d' % batch)
+    skw = {k: kw.pop(k) for k in _PAGE_ARGS if k in kw}
+    if mgp is None and skw.get('text_key', 'rec') in ('mgp_text', 'mgp_lex'):
+        raise ValueError('text_key=%r needs a recogniser: pass mgp=' % skw['text_key'])
+    bins = kw.pop('bins', None)
+    bins = int(args.num_bins if bins is None else bins)
+    if skw.get('device') is None and skw.get('scorer') is None:
+        skw['device'] = next(model.parameters()).device
+    from . import inference as inf
+    pre, resizer, records = kw.pop('preprocessor', None), kw.pop('resizer', None), []
+    names = kw.pop('file_names', None)
+    if names is None:
+        names = [str(b) for b in range(len(images_u8))]
+    for lo in range(0, len(images_u8), batch):
+        imgs = list(images_u8[lo:lo + batch])
+        if mgp is None:
+            recs, pre = inf.predict_images(model, imgs, args, file_names=names[lo:lo + batch], preprocessor=pre, **kw)
+        else:
+            from .two_stage import spot_and_recognize
+            recs, pre, resizer = spot_and_recognize(model, mgp, imgs, args, file_names=names[lo:lo + batch], preprocessor=pre, resizer=resizer, **kw)
+        records.extend(recs)
+    if settings is None:
+        skw.pop('reader', None)
+        out = score_page_text(records, gt_texts, **skw)
+    else:
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images_u8]
+        out = sweep_reading(records, sizes, bins, gt_texts, settings, **skw)
     out['records'] = records
     return out

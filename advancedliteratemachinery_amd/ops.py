@@ -858,6 +858,37 @@ def split_match_ints(ints, n, n_groups, n_thr):
     return ints[:c].reshape(n_groups, n_thr, 4), ints[c:c + n], ints[c + n:c + 2 * n]
 
 
+PAGE_TEXT_SLICE_BYTES = 32768   # omp_page_edit_distance: scratch per pair (csrc/page_text.hip: PT_SLICE_BYTES)
+
+
+def page_scratch_bytes(n_pairs):
+    """the scratch omp_page_edit_distance needs for n_pairs pairs: two carry buffers per pair, whatever the pairs' lengths (the lengths live
+    in device memory; the entry point checks this size before it launches)"""
+    return max(int(n_pairs), 0) * PAGE_TEXT_SLICE_BYTES
+
+
+def page_edit_distance(pool, pool_bytes, a_off, a_len, b_off, b_len, sigma, scratch, dist=None):
+    """omp_page_edit_distance (csrc/page_text.hip; utils/page_text.py holds the specification): pool uint8 with pool_bytes valid codes
+    (0 .. sigma - 1, or 255 = equals nothing), a_off / a_len / b_off / b_len int32 [P], scratch uint8 with at least page_scratch_bytes(P)
+    bytes -> dist int32 [P]: the Levenshtein distance of every pair, -1 for a pair whose lengths or ranges are out of bounds."""
+    P = int(a_len.numel())
+    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('a_off', a_off, torch.int32, P), ('a_len', a_len, torch.int32, P),
+                                  ('b_off', b_off, torch.int32, P), ('b_len', b_len, torch.int32, P), ('scratch', scratch, torch.uint8, 0)):
+        if t is None:
+            raise ValueError('%s is missing' % name)
+        _c(t, name)
+        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if dist is None:
+        dist = torch.empty(max(P, 1), dtype=torch.int32, device=a_len.device)
+    elif dist.dtype != torch.int32 or dist.numel() < P or not dist.is_contiguous():
+        raise ValueError('dist must be a contiguous int32 tensor with at least %d elements' % P)
+    rc = _lib.lib().omp_page_edit_distance(ptr(pool), int(pool_bytes), ptr(a_off), ptr(a_len), ptr(b_off), ptr(b_len), P, int(sigma), ptr(scratch),
+                                           int(scratch.numel()), ptr(dist), stream())
+    _lib.check(rc, 'omp_page_edit_distance')
+    return dist[:P]
+
+
 def _reading_tables(polys, tables, host_tables, n_groups):
     N, G = int(polys.shape[0]), int(n_groups)
     for name, tt, numel in (('polys', polys, 32 * N), ('tables', tables, 3 * G + 1)):

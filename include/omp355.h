@@ -742,6 +742,25 @@ int omp_spotting_match(const int32_t* inter, const int64_t* inter_start, const i
                        const int32_t* gt_dc, const int32_t* text, const int32_t* level, int n, int n_groups, int n_thr, int t_iou,
                        int t_dc, int report, int32_t* counts, int32_t* det_gt, int32_t* gt_det, omp_stream_t s);
 
+/* ---- page text scoring: the Levenshtein distance of whole pages ----
+ * The reference scores a parsed page as 1 - edit_distance(pred, gt) / max(len(pred), len(gt)) on strings without blanks and newlines
+ * (Benchmarks/CC-OCR/evaluation/evaluator/doc_parsing_evaluator.py:223-238).  utils/page_text.py holds the specification (distance_cpu,
+ * pairs_cpu); this entry point equals it on every integer.  Insert / delete / substitute cost 1.
+ *   pool, pool_bytes   uint8 character codes: 0 .. sigma - 1, or 255, which equals nothing (itself included).  A code in sigma .. 254
+ *                      is outside the contract and is treated like 255.
+ *   a_off, a_len, b_off, b_len   int32 [n_pairs]: pair p is pool[a_off, a_off + a_len) against pool[b_off, b_off + b_len); ranges may
+ *                      overlap and be shared between pairs.  Lengths 0 .. 65535.
+ *   sigma              0 .. 254: the dynamic LDS of a workgroup is (sigma + 1) * 512 bytes
+ *   scratch            8-byte aligned, at least n_pairs * 32768 bytes (pair p's carries between stripes of 4096 characters of a)
+ *   dist               int32 [n_pairs], written in full
+ * OMP_ERR_INVALID, nothing launched: a null pointer, n_pairs < 1, sigma outside 0 .. 254, too little scratch.  The tables live in
+ *   device memory, so what only they show is REFUSED on the device: a pair with a negative length, a length above 65535 or a range
+ *   outside the pool gets dist = -1 and reads nothing of the pool.
+ * One launch, one wave per pair; no allocation, no synchronisation, no atomics. */
+int omp_page_edit_distance(const uint8_t* pool, int64_t pool_bytes, const int32_t* a_off, const int32_t* a_len, const int32_t* b_off,
+                           const int32_t* b_len, int n_pairs, int sigma, void* scratch, int64_t scratch_bytes, int32_t* dist,
+                           omp_stream_t s);
+
 /* ---- reading order: words -> text lines -> the order a reader takes them in ----
  * Neither reference project orders its words: they leave the engine in decoder order.  utils/reading.py holds the specification
  * (features_cpu, links_cpu, lines_cpu); every output integer equals it.  Integers only.
