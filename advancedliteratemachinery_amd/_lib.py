@@ -81,6 +81,7 @@ _SIGS = {
     'omp_abi_version': (c_int, []),
     'omp_layernorm': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
                               c_int, c_float, c_void_p]),
+    'omp_layernorm_sampled': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_void_p]),
     'omp_gemm_bias_act': (c_int, [ctypes.POINTER(GemmArgs), c_void_p]),
     'omp_swin_mlp_fused': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int, c_int, c_void_p]),
@@ -98,6 +99,7 @@ _SIGS = {
     'omp_patch_merge_gather_ln2': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_void_p]),
     'omp_split_bf16': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
     'omp_fpn_fuse': (c_int, [c_void_p] * 5 + [c_int] * 11 + [c_void_p]),
+    'omp_fpn_fuse_sampled': (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     'omp_mask_nearest': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'omp_sine_posembed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'omp_dec_embed_ln': (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_void_p]),

@@ -35,9 +35,12 @@ struct LnP {
   int split;   // y is bf16 and holds split pairs: row pitch 2C, hi at column c, lo at column C + c (OMP_BF16X2)
   // gather mode (PatchMerging): x is [B,H,W,Cin], row = (b, y2, x2), C = 4*Cin
   int gather; int H, W, Cin, H2, W2;
+  // sample mode (SAMPLE kernels, the FPN neck's stage-output norm): x is [B,H,W,C], output row (b, yq, xq) of a compact [B,H2,W2,C] map
+  // is the LayerNorm of pixel (b, y(yq), x(xq)), y(q) = (q / sgroup) * sstep + q % sgroup: the first sgroup of every sstep rows / columns
+  int sstep, sgroup;
 };
 
-template <typename TI, typename TO, int IT>
+template <typename TI, typename TO, int IT, bool SAMPLE = false>
 __global__ __launch_bounds__(256) void ln_kernel(LnP p) {
   constexpr int NV = Vec16<TI>::N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -57,6 +60,14 @@ __global__ __launch_bounds__(256) void ln_kernel(LnP p) {
     gy = (int)(r % p.H2); gb = (int)(r / p.H2);
     cpp = p.Cin / NV;  // chunks per part
   }
+  int64_t srow = row;   // the input row of this output row
+  if constexpr (SAMPLE) {
+    int64_t r = rvalid ? row : 0;
+    const int xq = (int)(r % p.W2); r /= p.W2;
+    const int yq = (int)(r % p.H2), b = (int)(r / p.H2);
+    const int yy = (yq / p.sgroup) * p.sstep + yq % p.sgroup, xx = (xq / p.sgroup) * p.sstep + xq % p.sgroup;
+    srow = ((int64_t)b * p.H + yy) * p.W + xx;
+  }
 
   float v[IT][NV];
   float s = 0.f;
@@ -74,7 +85,7 @@ __global__ __launch_bounds__(256) void ln_kernel(LnP p) {
         else
           ok = false;  // zero padding (F.pad), still counted in the statistics
       } else {
-        src = X + row * p.C + c * NV;
+        src = X + srow * p.C + c * NV;
       }
     }
     if (ok) {
@@ -131,7 +142,7 @@ __global__ __launch_bounds__(256) void ln_kernel(LnP p) {
   }
 }
 
-template <typename TI, typename TO>
+template <typename TI, typename TO, bool SAMPLE = false>
 int launch_ln(LnP p, hipStream_t st, const char* name) {
   constexpr int NV = Vec16<TI>::N;
   OMP_CHECK_ARG(p.C % NV == 0 && p.C % 4 == 0, "%s: C=%d must be a multiple of %d", name, p.C, NV);
@@ -144,23 +155,24 @@ int launch_ln(LnP p, hipStream_t st, const char* name) {
   const int rpw = 64 >> lg;
   const int64_t blocks = ceil_div64(p.rows, 4 * rpw);
   dim3 grid((unsigned)blocks), block(256);
-  if (it <= 1) hipLaunchKernelGGL((ln_kernel<TI, TO, 1>), grid, block, 0, st, p);
-  else if (it <= 2) hipLaunchKernelGGL((ln_kernel<TI, TO, 2>), grid, block, 0, st, p);
-  else if (it <= 4) hipLaunchKernelGGL((ln_kernel<TI, TO, 4>), grid, block, 0, st, p);
-  else if (it <= 8) hipLaunchKernelGGL((ln_kernel<TI, TO, 8>), grid, block, 0, st, p);
-  else if (it <= 16) hipLaunchKernelGGL((ln_kernel<TI, TO, 16>), grid, block, 0, st, p);
+  if (it <= 1) hipLaunchKernelGGL((ln_kernel<TI, TO, 1, SAMPLE>), grid, block, 0, st, p);
+  else if (it <= 2) hipLaunchKernelGGL((ln_kernel<TI, TO, 2, SAMPLE>), grid, block, 0, st, p);
+  else if (it <= 4) hipLaunchKernelGGL((ln_kernel<TI, TO, 4, SAMPLE>), grid, block, 0, st, p);
+  else if (it <= 8) hipLaunchKernelGGL((ln_kernel<TI, TO, 8, SAMPLE>), grid, block, 0, st, p);
+  else if (it <= 16) hipLaunchKernelGGL((ln_kernel<TI, TO, 16, SAMPLE>), grid, block, 0, st, p);
   else { omp_set_error("%s: C=%d too large", name, p.C); return OMP_ERR_UNSUPPORTED; }
   OMP_CHECK_LAUNCH(name);
   return OMP_OK;
 }
 
+template <bool SAMPLE = false>
 int dispatch_ln(LnP p, int x_dtype, int y_dtype, hipStream_t st, const char* name) {
   p.split = 0;
   if (y_dtype == OMP_BF16X2) { p.split = 1; y_dtype = OMP_BF16; }
-  if (x_dtype == OMP_F32 && y_dtype == OMP_F32) return launch_ln<float, float>(p, st, name);
-  if (x_dtype == OMP_F32 && y_dtype == OMP_BF16) return launch_ln<float, bf16_t>(p, st, name);
-  if (x_dtype == OMP_BF16 && y_dtype == OMP_BF16) return launch_ln<bf16_t, bf16_t>(p, st, name);
-  if (x_dtype == OMP_BF16 && y_dtype == OMP_F32) return launch_ln<bf16_t, float>(p, st, name);
+  if (x_dtype == OMP_F32 && y_dtype == OMP_F32) return launch_ln<float, float, SAMPLE>(p, st, name);
+  if (x_dtype == OMP_F32 && y_dtype == OMP_BF16) return launch_ln<float, bf16_t, SAMPLE>(p, st, name);
+  if (x_dtype == OMP_BF16 && y_dtype == OMP_BF16) return launch_ln<bf16_t, bf16_t, SAMPLE>(p, st, name);
+  if (x_dtype == OMP_BF16 && y_dtype == OMP_F32) return launch_ln<bf16_t, float, SAMPLE>(p, st, name);
   omp_set_error("%s: bad dtypes %d -> %d", name, x_dtype, y_dtype);
   return OMP_ERR_INVALID;
 }
@@ -426,6 +438,22 @@ extern "C" int omp_layernorm(const void* x, int x_dtype, const float* gamma, con
   p.gather = 0;
   if (y == nullptr) y_dtype = OMP_F32;
   return dispatch_ln(p, x_dtype, y_dtype, (hipStream_t)s, "omp_layernorm");
+}
+
+extern "C" int omp_layernorm_sampled(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype, int B, int H,
+                                     int W, int C, int step, int group, float eps, omp_stream_t s) {
+  OMP_CHECK_ARG(x && gamma && beta && y, "omp_layernorm_sampled: null pointer");
+  OMP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0, "omp_layernorm_sampled: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+  // every sampled pixel lies inside the map: the last group starts at H - step and ends at H - step + group - 1 <= H - 1
+  OMP_CHECK_ARG(group >= 1 && group <= step && H % step == 0 && W % step == 0,
+                "omp_layernorm_sampled: H=%d and W=%d must be multiples of step=%d, 1 <= group=%d <= step", H, W, step, group);
+  OMP_CHECK_ARG(y_dtype == OMP_F32 || y_dtype == OMP_BF16, "omp_layernorm_sampled: bad output dtype %d", y_dtype);
+  LnP p{};
+  p.x = x; p.g = gamma; p.b = beta; p.y = y; p.yf = nullptr; p.C = C; p.eps = eps;
+  p.gather = 0;
+  p.H = H; p.W = W; p.H2 = H / step * group; p.W2 = W / step * group; p.sstep = step; p.sgroup = group;
+  p.rows = (int64_t)B * p.H2 * p.W2;
+  return dispatch_ln<true>(p, x_dtype, y_dtype, (hipStream_t)s, "omp_layernorm_sampled");
 }
 
 extern "C" int omp_patch_merge_gather_ln(const void* x, const float* gamma, const float* beta, void* y,

@@ -199,8 +199,19 @@ class Encoder(object):
                 H, W = H2, W2
         return outs
 
-    def backbone(self, img):
-        """img [B,3,H,W] fp32 -> list of (normed map [B*h*w, C], h, w) per stage."""
+    # stage -> (step, group) of the rows / columns of its normed map that the stride-2 FPN neck reads on the regular geometry
+    # (csrc/fpn.hip, omp_fpn_fuse_sampled): c2 the bilinear taps {4t, 4t+1}, c3 the pixels 2t; c4 and c5 are read everywhere
+    NECK_SAMPLES = {0: (4, 2), 1: (2, 1)}
+
+    def neck_sampled(self, H, W):
+        """Does encode() of H x W images take the sampled neck?  bf16 engine with the FPN on the regular geometry h2 == 2 h3 == 4 h4 (and
+        the widths alike: PatchMerging halves with ceil, so h2 % 4 == 0 says it; every image side that is a multiple of 32 has it)."""
+        return (self.use_fpn and self.dtype == torch.bfloat16 and not self.x3
+                and ((H + 3) // 4) % 4 == 0 and ((W + 3) // 4) % 4 == 0)
+
+    def backbone(self, img, sample_neck=False):
+        """img [B,3,H,W] fp32 -> list of (normed map [B*h*w, C], h, w) per stage.  sample_neck (bf16 engine; encode() on neck_sampled
+        sizes): the maps of stages 0 and 1 hold only the NECK_SAMPLES pixels, [B*hq*wq, C] -- (h, w) stay the stage's full size."""
         if self.x3:
             return [(f, h, w) for _, h, w, f in self._backbone_x3(img, True)]
         B = img.shape[0]
@@ -251,7 +262,11 @@ class Encoder(object):
                     y = ops.layernorm(x, blk.n2g, blk.n2b, out=y, out_dtype=T, eps=LN_EPS)
                     h = self._gemm(y, blk.fc1_w, blk.fc1_b, act=ops.ACT_GELU)
                     self._gemm(h, blk.fc2_w, blk.fc2_b, residual=x, out=x)
-            outs.append((ops.layernorm(x, st.out_g, st.out_b, out=self._rows(x.shape[0], C, T, x.device), out_dtype=T, eps=LN_EPS), H, W))
+            if sample_neck and si in self.NECK_SAMPLES:
+                step, group = self.NECK_SAMPLES[si]
+                outs.append((ops.layernorm_sampled(x, st.out_g, st.out_b, B, H, W, step, group, out_dtype=T, eps=LN_EPS)[0], H, W))
+            else:
+                outs.append((ops.layernorm(x, st.out_g, st.out_b, out=self._rows(x.shape[0], C, T, x.device), out_dtype=T, eps=LN_EPS), H, W))
             if st.down_w is not None:
                 ym, H2, W2 = ops.patch_merge_gather_ln(x, st.down_g, st.down_b, B, H, W, C, LN_EPS, out_dtype=T)
                 x = self._gemm(ym, st.down_w, out_dtype=torch.float32)
@@ -271,11 +286,14 @@ class Encoder(object):
         per-shape cache.  out: optional (memory, mem_pos) destination views of a larger engine call (_encode_chunked)."""
         B = img.shape[0]
         x3 = self.x3
+        # the stride-2 neck reads a quarter of c2 and c3: normalise and project only those pixels (same arithmetic on fewer rows, so the
+        # memory is the full path's bit for bit); the intermediates a parity test asks for are the full maps
+        sampled = not want_intermediates and self.neck_sampled(img.shape[2], img.shape[3])
         if x3:
             sfeats = self._backbone_x3(img, want_intermediates)
             feats = [(f, h, w) for _, h, w, f in sfeats]
         else:
-            feats = self.backbone(img)
+            feats = self.backbone(img, sample_neck=sampled)
         if self.use_fpn:
             (c2, h2, w2), (c3, h3, w3), (c4, h4, w4), (c5, h5, w5) = feats
             if x3:
@@ -288,7 +306,10 @@ class Encoder(object):
                 l3 = self._gemm(c3, self.fpn_w[2])
                 l2 = self._gemm(c2, self.fpn_w[3])
             sizes = ((h2, w2), (h3, w3), (h4, w4), (h5, w5))
-            src, ho, wo = ops.fpn_fuse(l2, l3, l4, l5, B, sizes, 2)
+            if sampled:   # c2, c3 and so l2, l3 are the sampled maps
+                src, ho, wo = ops.fpn_fuse_sampled(l2, l3, l4, l5, B, sizes)
+            else:
+                src, ho, wo = ops.fpn_fuse(l2, l3, l4, l5, B, sizes, 2)
             lvl = (h4, w4)
             if (ho, wo) != lvl:
                 raise RuntimeError('stride-2 projection grid %s != stage-2 grid %s' % ((ho, wo), lvl))

@@ -56,6 +56,20 @@ def layernorm(x, gamma, beta, out_dtype=None, out=None, out_f32=None, eps=1e-5, 
     return out
 
 
+def layernorm_sampled(x, gamma, beta, B, H, W, step, group, out_dtype=None, eps=1e-5):
+    """x [B*H*W, C] -> LN of the rows and columns q * step + r (r < group) only, as a compact [B * hq * wq, C] map in `out_dtype`
+    (default x.dtype); -> (map, hq, wq).  omp_layernorm_sampled: the other pixels are never read."""
+    _c(x, 'x')
+    C = x.shape[-1]
+    if x.numel() != B * H * W * C:
+        raise ValueError('layernorm_sampled: x must hold B * H * W rows')
+    hq, wq = H // step * group, W // step * group
+    out = torch.empty((B * hq * wq, C), dtype=out_dtype or x.dtype, device=x.device)
+    rc = _lib.lib().omp_layernorm_sampled(ptr(x), dt(x), ptr(gamma), ptr(beta), ptr(out), dt(out), B, H, W, C, step, group, float(eps), stream())
+    _lib.check(rc, 'omp_layernorm_sampled')
+    return out, hq, wq
+
+
 def gemm(A, W, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None, M=None, lda=None,
          ldw=None, ldc=None, N=None, K=None, bias_row=None, bias_row_stride=0, trans_rows=0, trans_ld=0,
          ln=None, ln_eps=1e-5, small_m=False, store_mode=0, kv=None, bias_along_m=False, out_noresidual=None, a_wrap=0):
@@ -255,6 +269,19 @@ def fpn_fuse(l2, l3, l4, l5, B, sizes, stride):
                                  h4, w4, h5, w5, stride, stream())
     _lib.check(rc, 'omp_fpn_fuse')
     return out, ho, wo
+
+
+def fpn_fuse_sampled(l2s, l3s, l4, l5, B, sizes):
+    """fpn_fuse(..., stride=2) from the sampled laterals (omp_fpn_fuse_sampled): l3s [B*h4*w4, 256] holds l3's pixels (2ty, 2tx), l2s
+    [B*2h4*2w4, 256] l2's rows / columns {4t, 4t+1}; `sizes` are the FULL level sizes, which must be regular (h2 == 2 h3 == 4 h4)."""
+    (h2, w2), (h3, w3), (h4, w4), (h5, w5) = sizes
+    if l3s.shape[0] != B * h4 * w4 or l2s.shape[0] != 4 * B * h4 * w4:
+        raise ValueError('fpn_fuse_sampled: l3s must hold B * h4 * w4 rows and l2s four times as many')
+    out = torch.empty((B * h4 * w4, 1024), dtype=l2s.dtype, device=l2s.device)
+    rc = _lib.lib().omp_fpn_fuse_sampled(ptr(_c(l2s, 'l2s')), ptr(_c(l3s, 'l3s')), ptr(l4), ptr(l5), ptr(out), dt(l2s), B, h2, w2, h3, w3,
+                                         h4, w4, h5, w5, stream())
+    _lib.check(rc, 'omp_fpn_fuse_sampled')
+    return out, h4, w4
 
 
 def mask_nearest(mask_u8, h, w):

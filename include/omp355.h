@@ -53,6 +53,12 @@ int omp_abi_version(void);
 int omp_layernorm(const void* x, int x_dtype, const float* gamma, const float* beta, void* y,
                   int y_dtype, float* y_f32, int64_t rows, int C, float eps, omp_stream_t s);
 
+/* omp_layernorm of the pixels the FPN neck reads (omp_fpn_fuse_sampled): x is a token-major [B, H, W, C] map, y (OMP_F32 or
+ * OMP_BF16) the compact [B, H / step * group, W / step * group, C] map of the rows and columns q * step + r, r < group, in order;
+ * no other pixel of x is read.  H and W multiples of step, 1 <= group <= step.  A row's result is omp_layernorm's, bit for bit. */
+int omp_layernorm_sampled(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype, int B, int H,
+                          int W, int C, int step, int group, float eps, omp_stream_t s);
+
 /* ---- GEMM with fused epilogue ---------------------------------------------------------------
  * C[m,n] = act(sum_k A[m,k] * W[n,k] + bias[n]) + residual[m,n]
  * Replaces nn.Linear / 1x1 nn.Conv2d call sites: swin_transformer.py:127,148 (qkv, proj),
@@ -231,6 +237,13 @@ int omp_split_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int64_t ro
 int omp_fpn_fuse(const void* l2, const void* l3, const void* l4, const void* l5, void* out,
                  int dtype, int B, int h2, int w2, int h3, int w3, int h4, int w4, int h5, int w5,
                  int stride, omp_stream_t s);
+
+/* omp_fpn_fuse at stride 2 on the regular geometry h2 == 2 h3 == 4 h4 (and the widths alike; refused otherwise), reading only the
+ * lateral pixels that grid needs: l3s is the [B, h4, w4] map of l3's pixels (2 ty, 2 tx), l2s the [B, 2 h4, 2 w4] map of l2's rows and
+ * columns {4 t, 4 t + 1} (omp_layernorm_sampled with step / group = 2 / 1 and 4 / 2, then the lateral products); l4, l5 are whole.
+ * out [B, h4 * w4, 1024] equals omp_fpn_fuse's bit for bit; the p3 value under the four p2 taps of an output is summed once. */
+int omp_fpn_fuse_sampled(const void* l2s, const void* l3s, const void* l4, const void* l5, void* out, int dtype, int B, int h2,
+                         int w2, int h3, int w3, int h4, int w4, int h5, int w5, omp_stream_t s);
 
 /* ---- Padding mask at a feature level: nearest-neighbour resize, exactly F.interpolate(mask[None].float(), size=(h, w))
  * .to(torch.bool)[0] of swin_transformer.py:621 (source index = min(floor(dst * (float)H / h), H - 1)).
