@@ -774,6 +774,31 @@ int omp_page_edit_distance(const uint8_t* pool, int64_t pool_bytes, const int32_
                            const int32_t* b_len, int n_pairs, int sigma, void* scratch, int64_t scratch_bytes, int32_t* dist,
                            omp_stream_t s);
 
+/* ---- page search: fuzzy phrase matches in the text of read pages ----
+ * Sellers' approximate string matching, insert / delete / substitute cost 1: D[0][j] = 0, D[i][0] = i, v_j = D[m][j].
+ * utils/page_search.py holds the specification (row_cpu, search_cpu); this entry point equals it on every integer.
+ *   pool, pool_bytes   uint8 character codes: 0 .. sigma - 1, or 255, which equals nothing (itself included).  A code in sigma .. 254
+ *                      is outside the contract and is treated like 255.
+ *   page_off, page_len int32 [n_pages]: page p is pool[page_off, page_off + page_len), 0 .. 65535 characters
+ *   query_off, query_len, k   int32 [n_queries]: query q is pool[query_off, query_off + query_len), 1 .. 64 characters, with the
+ *                      tolerance 0 <= k <= query_len - 1.  Ranges may overlap and be shared.
+ *   jobs               int32 [n_jobs, 2]: (page, query); 1 .. 2^20 jobs
+ *   max_hits           H, 1 .. 64
+ *   scratch            8-byte aligned, at least n_jobs * 64 * max_hits * 8 bytes (per lane the first H hits of its chunk of the text)
+ *   best               int32 [n_jobs, 2] = (dist, end): the least v_j and the least j that attains it; (m, 0) for the empty match
+ *   n_hits             int32 [n_jobs]: the ends j in 1 .. n with v_j <= k, v_j <= v_{j-1} and (j == n or v_j < v_{j+1})
+ *   hits               int32 [n_jobs, H, 3] = (end, dist, start) of the first min(n_hits, H) hits in ascending end, the rest -1;
+ *                      start is the greatest s with edit_distance(query, text[s, end)) == dist
+ * OMP_ERR_INVALID, nothing launched: a null pointer, n_jobs outside 1 .. 2^20, no pages, no queries, sigma outside 0 .. 254, max_hits
+ *   outside 1 .. 64, too little scratch.  The tables live in device memory, so what only they show is REFUSED on the device: a job
+ *   whose page or query is not there, whose lengths are outside the limits, whose ranges lie outside the pool or whose k is outside
+ *   0 .. m - 1 gets n_hits = -1 (best and hits -1) and reads nothing of the pool.
+ * One launch, one wave per job; no allocation, no synchronisation, no atomics: the hits do not depend on scheduling. */
+int omp_page_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page_off, const int32_t* page_len, int n_pages,
+                    const int32_t* query_off, const int32_t* query_len, const int32_t* k, int n_queries, const int32_t* jobs,
+                    int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best, int32_t* n_hits,
+                    int32_t* hits, omp_stream_t s);
+
 /* ---- reading order: words -> text lines -> the order a reader takes them in ----
  * Neither reference project orders its words: they leave the engine in decoder order.  utils/reading.py holds the specification
  * (features_cpu, links_cpu, lines_cpu); every output integer equals it.  Integers only.
