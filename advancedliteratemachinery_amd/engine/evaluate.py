@@ -7,6 +7,8 @@ score thresholds (utils/scoring.py holds the protocol and 
                        depends on the order of the records (utils/page_text.py holds the specification)
     sweep_reading      the same records re-ordered under every candidate setting of the reading stage, all scored in ONE device call
     evaluate_reading   images + ground-truth texts -> engine calls of `batch`, then score_page_text or sweep_reading
+    align_page_text    the edit script behind score_page_text's distance: S / D / I counts, CER, confusions, per-word status and the boxes
+                       of the records that carry each ground-truth word (utils/page_align.py holds the specification)
 
 Agreement with the official ICDAR / Total-Text evaluation scripts has not been checked (they are not part of this project)."""
 import inspect
@@ -290,4 +292,85 @@ def evaluate_reading(model, images_u8, gt_texts, args, batch=8, mgp=None, settin
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images_u8]
         out = sweep_reading(records, sizes, bins, gt_texts, settings, **skw)
     out['records'] = records
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# page text alignment
+# ---------------------------------------------------------------------------------------------
+def _union_box(records):
+    pts = [p for r in records for p in r['polys']]
+    if not pts:
+        return None
+    xs, ys = [float(p[0]) for p in pts], [float(p[1]) for p in pts]
+    return (min(xs), min(ys), max(xs), max(ys))
+
+
+def _top(table, top):
+    """a {key: n} table -> the `top` most frequent as [(key, n)], ties by key"""
+    return sorted(table.items(), key=lambda kv: (-kv[1], kv[0]))[:max(int(top), 0)]
+
+
+def align_page_text(records, gt_texts, text_key='rec', strip=' \n', normalise=str.casefold, top=20, aligner=None, device=None):
+    """records and gt_texts: as score_page_text takes them.  Every image becomes one prediction string and one ground-truth string
+    (utils.page_align.page_words: every word stripped and normalised on its own, then concatenated) and the two are aligned by the
+    canonical optimal edit script (utils.page_align holds the rule).  aligner: a utils.page_align.PageAligner, or anything with its
+    `run` (HostPageAligner: the specification); default: one on `device` (default 'cuda').  All images go through ONE aligner.run.
+    -> dict(dist, len_pred, len_gt, match, sub, ins, dele int32 [G]; score, mean, micro as score_page_text gives them; cer = per image
+    (sub + ins + dele) / len_gt, None for an empty ground truth; cer_micro = the same over all images; word_precision = the CORRECT
+    prediction words over the non-empty ones; word_recall = the same over ground-truth words, None when every page's ground truth is one
+    string; confusions = dict(sub=[((pred_char, gt_char), n)], ins=[(char, n)], dele=[(char, n)]), the `top` most frequent over all
+    images; pages = per image dict(pred, gt = the aligned strings, pred_to_gt, gt_to_pred = the maps (-1: no partner), words = per
+    record dict(chars=(start, end) in pred, status, span = its images in gt or (-1, -1)), gt_words = per ground-truth word dict(text,
+    chars, status, span in pred, records=(first, last) = the records whose characters carry that span -- first the first record with
+    start + len > span[0], last the last with start < span[1] -- and box = (x0, y0, x1, y1), the union of their `polys` in pixels;
+    records and box are None for an ABSENT or EMPTY word)).  Statuses are utils.page_align.STATUS_NAMES."""
+    from ..utils import page_align as PA
+    from ..utils import page_text as PT
+    _check_page_records(records, gt_texts, text_key, 'align_page_text')
+    records = [list(recs) for recs in records]
+    pred = [PA.page_words(recs, text_key, strip, normalise) for recs in records]
+    truth = [PA.page_words(gt, 'text', strip, normalise) for gt in gt_texts]
+    pool, a_off, a_len, b_off, b_len, sigma = PT.encode_pairs([p[0] for p in pred], [t[0] for t in truth])
+    if aligner is None:
+        aligner = PA.PageAligner('cuda' if device is None else device)
+    res = aligner.run(pool, a_off, a_len, b_off, b_len, sigma)
+    counts = np.asarray(res['counts'], dtype=np.int32).reshape(-1, 4)
+    dist = counts[:, PA.SUB] + counts[:, PA.INS] + counts[:, PA.DEL]
+    out = _page_summary(dist, a_len, b_len)
+    out.update(match=counts[:, PA.MATCH].copy(), sub=counts[:, PA.SUB].copy(), ins=counts[:, PA.INS].copy(), dele=counts[:, PA.DEL].copy())
+    out['cer'] = [int(d) / int(n) if n else None for d, n in zip(dist.tolist(), b_len.tolist())]
+    out['cer_micro'] = int(dist.sum()) / int(b_len.sum()) if int(b_len.sum()) else None
+    conf = dict(sub={}, ins={}, dele={})
+    tally = dict(pred=[0, 0], gt=[0, 0])                                      # correct words, non-empty words
+    pages = []
+    for g, (recs, (ptext, p_start, p_len), (ttext, t_start, t_len)) in enumerate(zip(records, pred, truth)):
+        a_map, b_map = PA.split_maps(res, a_len, b_len, g)
+        for kind, table in PA.confusions(ptext, ttext, a_map, b_map).items():
+            for key, n in table.items():
+                conf[kind][key] = conf[kind].get(key, 0) + n
+        p_status, p_span = PA.word_report_cpu(a_map, p_start, p_len, ptext, ttext)
+        t_status, t_span = PA.word_report_cpu(b_map, t_start, t_len, ttext, ptext)
+        for side, status in (('pred', p_status), ('gt', t_status)):
+            tally[side][0] += int((status == PA.CORRECT).sum())
+            tally[side][1] += int((status != PA.EMPTY).sum())
+        p_end = p_start + p_len
+        words = [dict(chars=(int(s), int(e)), status=PA.STATUS_NAMES[st], span=(int(sp[0]), int(sp[1])))
+                 for s, e, st, sp in zip(p_start.tolist(), p_end.tolist(), p_status.tolist(), p_span.tolist())]
+        gt_words = []
+        for s, n, st, sp in zip(t_start.tolist(), t_len.tolist(), t_status.tolist(), t_span.tolist()):
+            w = dict(text=ttext[s:s + n], chars=(s, s + n), status=PA.STATUS_NAMES[st], span=(int(sp[0]), int(sp[1])), records=None, box=None)
+            if sp[0] >= 0:
+                first = int(np.searchsorted(p_end, sp[0], side='right'))         # the first record with start + len > span[0]
+                last = int(np.searchsorted(p_start, sp[1], side='left')) - 1    # the last record with start < span[1]
+                w['records'] = (first, last)
+                w['box'] = _union_box(recs[first:last + 1])
+            gt_words.append(w)
+        pages.append(dict(pred=ptext, gt=ttext, pred_to_gt=np.asarray(a_map, dtype=np.int32), gt_to_pred=np.asarray(b_map, dtype=np.int32), words=words,
+                          gt_words=gt_words))
+    out['word_precision'] = tally['pred'][0] / tally['pred'][1] if tally['pred'][1] else None
+    one_string = all(isinstance(gt, str) for gt in gt_texts)
+    out['word_recall'] = None if one_string or not tally['gt'][1] else tally['gt'][0] / tally['gt'][1]
+    out['confusions'] = {kind: _top(table, top) for kind, table in conf.items()}
+    out['pages'] = pages
     return out

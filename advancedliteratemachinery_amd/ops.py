@@ -916,7 +916,44 @@ def page_edit_distance(pool, pool_bytes, a_off, a_len, b_off, b_len, sigma, scra
     return dist[:P]
 
 
-PAGE_SEARCH_CHUNK = 128         # omp_page_search: text columns per lane (csrc/page_search.hip: PS_CHUNK)
+PAGE_ALIGN_CARRY_BYTES = 32768  # omp_page_align: the head of a pair's scratch (csrc/page_align.hip: PA_CARRY_BYTES)
+PAGE_ALIGN_CELL_BYTES = 16      # omp_page_align: the record of one (64-row block, text column) (csrc/page_align.hip: PA_CELL_BYTES)
+
+
+def page_align_scratch_bytes(la, lb):
+    """the scratch omp_page_align needs for ONE pair of la x lb characters: the carries between stripes and two 64-bit words per
+    (64-row block of a, column of b).  The device checks scratch_off[p] + this against scratch_bytes for every pair."""
+    la, lb = max(int(la), 0), max(int(lb), 0)
+    return PAGE_ALIGN_CARRY_BYTES + PAGE_ALIGN_CELL_BYTES * ((la + 63) // 64) * lb
+
+
+def page_align(pool, pool_bytes, a_off, a_len, b_off, b_len, map_off, scratch_off, sigma, scratch, maps, maps_len=None, counts=None):
+    """omp_page_align (csrc/page_align.hip; utils/page_align.py holds the specification): pool uint8 with pool_bytes valid codes
+    (0 .. sigma - 1, or 255 = equals nothing), a_off / a_len / b_off / b_len int32 [P], map_off / scratch_off int64 [P] (pair p owns
+    maps[map_off[p] : map_off[p] + la + lb] and page_align_scratch_bytes(la, lb) bytes of scratch from scratch_off[p], a multiple of 8),
+    scratch uint8, maps int32 with maps_len entries (default: all of it) -> counts int32 [P, 4] = (match, sub, ins, del); maps holds
+    a_map then b_map of every pair.  A pair whose lengths, ranges or slices are out of bounds gets counts of -1 and writes nothing."""
+    P = int(a_len.numel())
+    maps_len = int(maps.numel()) if maps_len is None else int(maps_len)
+    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('a_off', a_off, torch.int32, P), ('a_len', a_len, torch.int32, P),
+                                  ('b_off', b_off, torch.int32, P), ('b_len', b_len, torch.int32, P), ('map_off', map_off, torch.int64, P),
+                                  ('scratch_off', scratch_off, torch.int64, P), ('scratch', scratch, torch.uint8, 0), ('maps', maps, torch.int32, maps_len)):
+        if t is None:
+            raise ValueError('%s is missing' % name)
+        _c(t, name)
+        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if counts is None:
+        counts = torch.empty(4 * max(P, 1), dtype=torch.int32, device=a_len.device)
+    elif not counts.is_cuda or counts.dtype != torch.int32 or counts.numel() < 4 * P or not counts.is_contiguous():
+        raise ValueError('counts must be a contiguous device int32 tensor with at least %d elements' % (4 * P))
+    rc = _lib.lib().omp_page_align(ptr(pool), int(pool_bytes), ptr(a_off), ptr(a_len), ptr(b_off), ptr(b_len), ptr(map_off), ptr(scratch_off), P, int(sigma),
+                                   ptr(scratch), int(scratch.numel()), ptr(maps), maps_len, ptr(counts), stream())
+    _lib.check(rc, 'omp_page_align')
+    return counts.reshape(-1)[:4 * P].view(P, 4)
+
+
+PAGE_SEARCH_CHUNK = 128        # omp_page_search: text columns per lane (csrc/page_search.hip: PS_CHUNK)
 PAGE_SEARCH_HIT_BYTES = 512     # omp_page_search: scratch per job and kept hit: 64 lanes x (end, dist)
 
 

@@ -799,6 +799,32 @@ int omp_page_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page
                     int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best, int32_t* n_hits,
                     int32_t* hits, omp_stream_t s);
 
+/* ---- page text alignment: the optimal edit script of whole pages ----
+ * The script behind omp_page_edit_distance's number: a is the prediction (rows i), b the ground truth (columns j), D the Levenshtein
+ * table with D[i][0] = i and D[0][j] = j.  The walk runs from (la, lb) to (0, 0) and takes the FIRST rule that applies:
+ *   1. i > 0, j > 0, D[i-1][j-1] + (a_i != b_j) == D[i][j]: MATCH or SUB, a_map[i-1] = j-1, b_map[j-1] = i-1
+ *   2. i > 0, D[i-1][j] + 1 == D[i][j]: INS, a_map[i-1] = -1            3. otherwise DEL, b_map[j-1] = -1
+ * utils/page_align.py holds the specification (align_cpu, pairs_align_cpu); this entry point equals it on every integer.
+ *   pool, pool_bytes   uint8 character codes, as omp_page_edit_distance takes them (255 equals nothing, itself included)
+ *   a_off, a_len, b_off, b_len   int32 [n_pairs]: pair p is pool[a_off, a_off + a_len) against pool[b_off, b_off + b_len); ranges may
+ *                      overlap and be shared between pairs.  Lengths 0 .. 65535.
+ *   map_off            int64 [n_pairs]: pair p owns maps[map_off, map_off + a_len + b_len), a_map first and b_map after it
+ *   scratch_off        int64 [n_pairs], multiples of 8: pair p owns 32768 + 16 * ceil(a_len / 64) * b_len bytes of scratch from there
+ *                      (the carries between stripes, then per 64-row block and text column two 64-bit words: diagonal allowed, dv = +1)
+ *   sigma              0 .. 254: the dynamic LDS of a workgroup is (sigma + 1) * 512 bytes
+ *   scratch            8-byte aligned, scratch_bytes bytes; the slices of two pairs must not overlap
+ *   maps, maps_len     int32 [maps_len]; entries no pair owns are left as they are
+ *   counts             int32 [n_pairs][4] = (match, sub, ins, del), written in full; sub + ins + del is the distance
+ * OMP_ERR_INVALID, nothing launched: a null pointer, n_pairs outside 1 .. 2^24, sigma outside 0 .. 254, pool_bytes, maps_len or
+ *   scratch_bytes negative, scratch not 8-byte aligned.  The tables live in device memory, so what only they show is REFUSED on the
+ *   device: a pair with a negative length, a length above 65535, a range outside the pool, a negative map_off or a slice past maps_len,
+ *   a scratch_off that is negative or no multiple of 8, or a slice past scratch_bytes gets counts = -1 four times, reads nothing of
+ *   the pool and writes nothing to maps or scratch.
+ * One launch, one wave per pair; no allocation, no synchronisation, no atomics: the script does not depend on scheduling. */
+int omp_page_align(const uint8_t* pool, int64_t pool_bytes, const int32_t* a_off, const int32_t* a_len, const int32_t* b_off,
+                   const int32_t* b_len, const int64_t* map_off, const int64_t* scratch_off, int n_pairs, int sigma, void* scratch,
+                   int64_t scratch_bytes, int32_t* maps, int64_t maps_len, int32_t* counts, omp_stream_t s);
+
 /* ---- reading order: words -> text lines -> the order a reader takes them in ----
  * Neither reference project orders its words: they leave the engine in decoder order.  utils/reading.py holds the specification
  * (features_cpu, links_cpu, lines_cpu); every output integer equals it.  Integers only.
