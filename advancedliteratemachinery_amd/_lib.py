@@ -30,7 +30,8 @@ class GemmArgs(ctypes.Structure):
                 ('trans_rows', c_int64), ('trans_ld', c_int64), ('ln_gamma', c_void_p), ('ln_beta', c_void_p),
                 ('ln_eps', c_float), ('small_m_splitk', c_int32), ('store_mode', c_int32), ('bias_along_m', c_int32),
                 ('kv_images', c_int32), ('kv_tokens', c_int32), ('kv_mpad', c_int32), ('kv_heads', c_int32),
-                ('kv_key_block', c_int32), ('C2', c_void_p), ('ldc2', c_int64), ('a_wrap', c_int32)]
+                ('kv_key_block', c_int32), ('C2', c_void_p), ('ldc2', c_int64), ('a_wrap', c_int32),
+                ('bias_row_mod', c_int32), ('bias_row_off', c_int32)]
 
 
 class SampleCfg(ctypes.Structure):
@@ -53,7 +54,7 @@ class DecRowsArgs(ctypes.Structure):
                 ('prologue', c_int32), ('tail', c_int32), ('ff1_b', c_void_p), ('ff2_b', c_void_p), ('seq', c_void_p), ('seq_ld', c_int32),
                 ('word_emb', c_void_p), ('pos_tab', c_void_p), ('emb_g', c_void_p), ('emb_b', c_void_p), ('lnt_g', c_void_p), ('lnt_b', c_void_p),
                 ('bias_tab', c_void_p), ('qkv', c_void_p), ('h0_b', c_void_p), ('h1_b', c_void_p), ('h2_b', c_void_p), ('logits', c_void_p),
-                ('vocab', c_int32), ('x3', c_int32), ('xcd_mask', c_int32)]
+                ('vocab', c_int32), ('x3', c_int32), ('xcd_mask', c_int32), ('pos_mod', c_int32)]
 
 
 class SwinRowsArgs(ctypes.Structure):
@@ -74,7 +75,10 @@ class DecoderPlan(ctypes.Structure):
                    ('d_pos', c_void_p), ('probs', c_void_p), ('finished', c_void_p), ('lengths', c_void_p)]
                 + [(n, c_void_p) for n in ('x', 'x2', 'y', 'qkv', 'att', 'q', 'ffh', 'hh0', 'hh1',
                                            'partial', 'logits')]
-                + [('sample', SampleCfg)])
+                + [('sample', SampleCfg)]
+                # the batched prompt prefill (include/omp355.h): switch, tiles table, scratch of pf_rows rows
+                + [('prefill', c_int32), ('n_prefill_tiles', c_int32), ('prefill_tiles', c_void_p), ('pf_rows', c_int64)]
+                + [(n, c_void_p) for n in ('pf_x', 'pf_qkv', 'pf_att', 'pf_q', 'pf_ffh', 'pf_partial')])
 
 
 _SIGS = {
@@ -135,6 +139,8 @@ _SIGS = {
                                   [c_int, c_void_p]),
     'omp_debug_sample_impl': (c_int, [c_int]),
     'omp_debug_dec_fused': (c_int, [c_int]),
+    'omp_debug_prefill': (c_int, [c_int]),
+    'omp_debug_prefill_passes': (c_int64, []),
     'omp_vit_patch_embed': (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     'omp_vit_attn_qkv': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     'omp_vit_attn': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),

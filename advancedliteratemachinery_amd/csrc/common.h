@@ -86,6 +86,8 @@ struct omp_ctx {
   unsigned long long* gemm_trace = nullptr;   // device buffers of the TRACE instantiations
   long long gemm_trace_cap = 0;
   unsigned long long* mlp_trace = nullptr;
+  int prefill = 0;           // 0 = the batched prompt prefill where a plan asks for it and is eligible (csrc/decoder.hip: prefill_launch), 1 = stepwise always (omp_debug_prefill)
+  long long prefill_passes = 0;   // batched passes this context has launched (omp_debug_prefill_passes: the tests assert which path ran)
   int rows_rtt = 0;          // decoder chains: 16-row tiles per workgroup, 0 = by row count (csrc/dec_rows.hip rows_rtt), 2..5 forced (omp_debug_rows_tile)
   OmpGraphSlot slots[OMP_MAX_GRAPH_SLOTS];
   int prof_mask = 0;

@@ -599,12 +599,16 @@ struct RowsP {
   float* logits; int vocab;        // [R, vocab] fp32
   unsigned long long* trace;       // development (omp_debug_swin_mlp_trace): [workgroup][16] cycle sums of wave 0 per phase of dec_rows_ffn_kernel
   int xcd_mask;                    // XCDs that run the launch's tiles (rows_common.inc xcd_tile); 0 = every block is a tile
+  int pos_mod;                     // mid, ROWPOS: row r sits at position r % pos_mod (the batched prompt prefill, csrc/decoder.hip)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // x' = x + att Wo^T + bo;  q = out_t(LayerNorm2(x') Wq^T + qbias[pos])          stream: Wo (64 fragments per wave and plane), Wq (64)
 // ---------------------------------------------------------------------------------------------------------------------
-template <int RTT, typename E>
+// ROWPOS (bf16 chains; the batched prompt prefill): row r takes qbias[r % pos_mod] and d_pos is not read.  The row's bias quad is added to its accumulator
+// quad where the one-position form adds its bias register, and the store then adds -0.0f, which changes no value and no sign: a row's q bits are the bits
+// of the one-position launch at that row's position.
+template <int RTT, typename E, bool ROWPOS = false>
 __global__ __launch_bounds__(NW * 64) void dec_rows_mid_kernel(RowsP p) {
   constexpr int RT = RTT * 16, TILE_PLANE = plane_bytes(RT, A_PITCH);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -618,7 +622,8 @@ __global__ __launch_bounds__(NW * 64) void dec_rows_mid_kernel(RowsP p) {
   Stream st = stream_of_wave(p.wstream, p.wave_stride, wave, lane);
   u32x4 ring[E::PF];
   sfor<E::PF>([&](auto U) { ws_issue<decltype(U)::value>(ring, st); });
-  const int pos = E::mid_pos(p.d_pos);
+  int pos = 0;
+  if constexpr (!ROWPOS) pos = E::mid_pos(p.d_pos);
 
   E::template stage<RTT>(p.att, r0, p.R, tile, wave, lane);
   lds_barrier();
@@ -631,9 +636,22 @@ __global__ __launch_bounds__(NW * 64) void dec_rows_mid_kernel(RowsP p) {
   ln_acc_to_tile<RTT, E>(acc, p.ln_g, p.ln_b, p.eps, tile, red, wave, li, g);
   zero_acc(acc);
   f32x4 qb[4];
-  load_bias<4>(qb, p.qbias_tab + (int64_t)pos * D, wave * 64, D, g);
+  if constexpr (!ROWPOS) load_bias<4>(qb, p.qbias_tab + (int64_t)pos * D, wave * 64, D, g);
   E::template pass<4, 16, RTT, A_PITCH>(acc, a_lane, ring, st);
   ws_drain(ring);
+  if constexpr (ROWPOS) {
+#pragma unroll
+    for (int rt = 0; rt < RTT; ++rt) {
+      const float* qrow = p.qbias_tab + (int64_t)(((int)r0 + rt * 16 + li) % p.pos_mod) * D + wave * 64 + g * 4;   // rows beyond R: some table row, never stored
+#pragma unroll
+      for (int ft = 0; ft < 4; ++ft) {
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(qrow + ft * 16);
+        acc[ft][rt] = f32x4{acc[ft][rt][0] + b4[0], acc[ft][rt][1] + b4[1], acc[ft][rt][2] + b4[2], acc[ft][rt][3] + b4[3]};
+      }
+    }
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft) qb[ft] = f32x4{-0.0f, -0.0f, -0.0f, -0.0f};
+  }
   E::template store<4, RTT, typename E::out_t>(acc, qb, static_cast<typename E::out_t*>(p.q) + r0 * D, D, nrow, wave * 64, D, li, g);
   if (E::MID_END_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -918,11 +936,11 @@ int launch_ffn(const RowsP& p, hipStream_t st) {
   else return launch(Int<E::RTT_MAX>());
 }
 
-template <int RTT, typename E>
+template <int RTT, typename E, bool ROWPOS = false>
 int launch_mid_t(RowsP p, hipStream_t st) {
   constexpr int RT = RTT * 16;
   const size_t smem = (size_t)E::PLANES * plane_bytes(RT, A_PITCH) + 2 * NW * RT * 4;
-  constexpr auto kern = dec_rows_mid_kernel<RTT, E>;
+  constexpr auto kern = dec_rows_mid_kernel<RTT, E, ROWPOS>;
   if (const int rc = omp_raise_lds<kern>(E::MID_NAME)) return rc;
   const int64_t n_tiles = ((int64_t)p.R + RT - 1) / RT;
   const unsigned grid = E::XCD ? xcd_grid(n_tiles, p.xcd_mask, &p.xcd_mask) : (unsigned)n_tiles;
@@ -940,7 +958,7 @@ RowsP rows_params(const omp_dec_rows_args* a) {
   p.seq = a->seq; p.seq_ld = a->seq_ld; p.word_emb = a->word_emb; p.pos_tab = a->pos_tab; p.emb_g = a->emb_g; p.emb_b = a->emb_b;
   p.lnt_g = a->lnt_g; p.lnt_b = a->lnt_b; p.bias_tab = a->bias_tab; p.qkv = a->qkv;
   p.h0_b = a->h0_b; p.h1_b = a->h1_b; p.h2_b = a->h2_b; p.logits = a->logits; p.vocab = a->vocab;
-  p.xcd_mask = a->xcd_mask;
+  p.xcd_mask = a->xcd_mask; p.pos_mod = a->pos_mod;
   return p;
 }
 RowsP rows_params(const omp_swin_rows_args* a) {
@@ -960,6 +978,9 @@ int rows_mid(const omp_dec_rows_args* a, hipStream_t st) {
   constexpr int EL = 2 * E::PLANES;
   OmpProfScope prof(OMP_PROF_ROWS, st, E::PRODUCTS * 4.0 * (double)a->R * D * D, (double)a->R * D * (EL + 4 + 4 + EL) + 2.0 * D * D * EL);
   const RowsP p = rows_params(a);
+  if constexpr (std::is_same<E, Bf16Rows>::value) {
+    if (p.pos_mod > 0) return E::template decoder_rows<1>(p.R, [&](auto RTT) { return launch_mid_t<decltype(RTT)::value, E, true>(p, st); });
+  }
   return E::template decoder_rows<1>(p.R, [&](auto RTT) { return launch_mid_t<decltype(RTT)::value, E>(p, st); });
 }
 
@@ -993,6 +1014,7 @@ int omp_rows_tile() { return RTT_DEFAULT * 16; }
 extern "C" int omp_dec_rows_mid(const omp_dec_rows_args* a, omp_stream_t s) {
   OMP_CHECK_ARG(a != nullptr, "omp_dec_rows_mid: null argument block");
   OMP_CHECK_ARG(a->R > 0 && a->d_pos && a->x && a->att && a->wstream && a->out_b && a->ln_g && a->ln_b && a->qbias_tab && a->q, "omp_dec_rows_mid: null pointer");
+  OMP_CHECK_ARG(a->pos_mod >= 0 && (a->pos_mod == 0 || !a->x3), "omp_dec_rows_mid: pos_mod (the per-row position, %d) goes with the bf16 chains", a->pos_mod);
   const int mul = a->x3 ? 2 : 1;
   OMP_CHECK_ARG(a->wave_stride == (int64_t)mul * 128 * 1024 && ((uintptr_t)a->wstream % 16) == 0,
                 "omp_dec_rows_mid: a wave's stream holds %d fragments of 1 KB (wave_stride %lld: not what model/packing.py::pack_rows_mid returns)", mul * 128, (long long)a->wave_stride);

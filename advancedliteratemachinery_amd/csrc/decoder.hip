@@ -24,20 +24,21 @@ constexpr int DH = 64;  // decoder head_dim (512 / 8)
 
 // ---------------------------------------------------------------------------------------------
 // embedding + LayerNorm  (one wave per row)
+// ROWPOS (the batched prompt prefill, prefill_launch below): row r is plan row r / pos_mod at position r % pos_mod; d_pos is not read
 // ---------------------------------------------------------------------------------------------
-template <typename TO>
+template <typename TO, bool ROWPOS = false>
 __global__ __launch_bounds__(256) void dec_embed_ln_kernel(const int32_t* __restrict__ seq, int seq_ld,
                                                            const int32_t* __restrict__ d_pos,
                                                            const float* __restrict__ word,
                                                            const float* __restrict__ postab,
                                                            const float* __restrict__ g,
                                                            const float* __restrict__ be, float* __restrict__ x,
-                                                           TO* __restrict__ y, int R, int d, float eps) {
+                                                           TO* __restrict__ y, int R, int d, float eps, int pos_mod = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int p = *d_pos;
-  const int tok = seq[(int64_t)r * seq_ld + p];
+  const int p = ROWPOS ? r % pos_mod : *d_pos;
+  const int tok = seq[(int64_t)(ROWPOS ? r / pos_mod : r) * seq_ld + p];
   const float* we = word + (int64_t)tok * d;
   const float* pe = postab + (int64_t)p * d;
   float v[4][4];
@@ -108,18 +109,23 @@ __device__ __forceinline__ void store8(bf16_t* p, const float* v) {
 // lane = (js = lane>>3 : key slot, dc = lane&7 : 8-dim chunk); 8 keys per iteration, each key row
 // (64 dims) read as 8 x 16 B (bf16) -- full 128-byte lines.  Online softmax per key slot, merged
 // across the 8 slots at the end.
+// PREFILL (the batched prompt prefill, prefill_launch below): blockIdx.x is PREFILL ROW r * L + j = plan row r at position j, of qkv / out
+// [R * L] rows.  The wave appends its own k / v at cache position j of row r and attends keys 0 .. j in the step's order -- the same
+// 32-key outer loop, key slots and merge -- taking keys i < j from the q | k | v rows of the same pass (qkv[r * L + i]: the bf16 values
+// the cache holds once that row's wave has stored them), so that no wave waits for another.  d_pos is not read.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool PREFILL = false>
 __global__ __launch_bounds__(256) void dec_self_attn_kernel(const T* __restrict__ qkv, T* __restrict__ kc,
                                                             T* __restrict__ vc, T* __restrict__ out,
                                                             const int32_t* __restrict__ d_pos, int R, int nH,
-                                                            int d, int Lmax) {
+                                                            int d, int Lmax, int L = 0) {
   // 4 heads of one row per workgroup (waves are independent; fewer, fatter workgroups dispatch faster)
-  const int r = blockIdx.x, h = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int rq = blockIdx.x, h = blockIdx.y * 4 + (threadIdx.x >> 6);   // rq: row of qkv / out
   if (h >= nH) return;
   const int lane = threadIdx.x & 63, js = lane >> 3, dc = lane & 7;
-  const int p = *d_pos;
-  const T* row = qkv + (int64_t)r * 3 * d + h * DH + dc * 8;
+  const int r = PREFILL ? rq / L : rq;                                  // row of the caches
+  const int p = PREFILL ? rq % L : *d_pos;
+  const T* row = qkv + (int64_t)rq * 3 * d + h * DH + dc * 8;
   float q[8], kn[8], vn[8];
   load8(row, q);
   load8(row + d, kn);
@@ -132,6 +138,10 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const T* __restrict_
     store8(kbase + (int64_t)p * d, kn);
     store8(vbase + (int64_t)p * d, vn);
   }
+  // keys before p: the caches, or (PREFILL) the k / v thirds of the pass's own rows of this plan row
+  const T* kprev = PREFILL ? row - (int64_t)p * 3 * d + d : kbase;
+  const T* vprev = PREFILL ? row - (int64_t)p * 3 * d + 2 * d : vbase;
+  const int64_t pitch = PREFILL ? 3 * (int64_t)d : d;
   float m = -INFINITY, l = 0.f, o[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = 0.f;
@@ -143,8 +153,8 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const T* __restrict_
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u * 8 + js;
       if (j < p) {
-        load8(kbase + (int64_t)j * d, kk[u]);
-        load8(vbase + (int64_t)j * d, vv[u]);
+        load8(kprev + j * pitch, kk[u]);
+        load8(vprev + j * pitch, vv[u]);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { kk[u][i] = kn[i]; vv[u][i] = vn[i]; }
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const T* __restrict_
     t += __shfl_xor(t, 8, 64); t += __shfl_xor(t, 16, 64); t += __shfl_xor(t, 32, 64);
     o[i] = t / l;
   }
-  if (js == 0) store8(out + (int64_t)r * d + h * DH + dc * 8, o);
+  if (js == 0) store8(out + (int64_t)rq * d + h * DH + dc * 8, o);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1939,6 +1949,104 @@ int step_launch(const omp_decoder_plan* P, bool do_head, hipStream_t st) {
   return OMP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batched prompt prefill (omp_decoder_plan.prefill, include/omp355.h): positions 0 .. n_prompt - 2 of the launch-per-Linear bf16 step as ONE
+// pass over R * L prefill rows, L = n_prompt - 1, row r * L + j = plan row r at position j.  A stepwise prefill streams every layer's K / V^T
+// slabs once per position past one live query row per image; all that the L steps leave behind is the self-attention cache rows 0 .. L - 1,
+// and the L rows of an image fit the 16-query tile of the same cross-attention kernel.  The pass runs, per row, the operations of
+// step_launch's branch in the same order: LayerNorm, bias adds and every Linear are row-local (a row's GEMM bits do not depend on M nor on
+// which of the 64 x 64 / 128 x 128 tile kernels runs it; at R <= 64 the step runs the split-K small-M kernel, and so does the pass, in
+// launches of 64 rows); the cross-attention columns of a 16-query tile are independent; the mid chain is bit-identical at every tile size.
+// The last layer stops behind its self-attention's cache append: nothing later reads what follows at these positions.
+// ---------------------------------------------------------------------------------------------
+constexpr int OMP_PREFILL_MAX_ROWS = 4096;   // R * L: below the row count from which gemm_auto_select may leave the 64 x 64 / 128 x 128 tile kernels (N <= 2048)
+
+bool prefill_eligible(const omp_decoder_plan* P) {
+  const omp_ctx& cx = omp_cur();
+  const int64_t L = P->n_prompt - 1;
+  return P->n_prompt >= 3 && P->dtype == OMP_BF16 && P->pre_norm && !P->rows_fused && !P->gemm_x3 && !P->kv_split && !fused_step_ok(P) &&
+         P->R >= 64 && P->R < 1024 && P->R * L <= OMP_PREFILL_MAX_ROWS && cx.force_gemm == 0 && cx.self_attn_impl != 2;
+}
+
+__global__ void set_pos_kernel(int32_t* d_pos, int pos) { *d_pos = pos; }
+
+// one Linear of the pass over the RL prefill rows: A [RL, K] (fp32 residual stream behind a LayerNorm prologue, else bf16) -> C [RL, N].  More
+// than 64 plan rows: one tiled product, as the step's; up to 64: the step's split-K small-M kernel on 64 rows per launch (its rows are
+// independent of M, not of the kernel).  bias_mod > 0: bias is a [positions, bias_stride] table, row m at position m % bias_mod
+int prefill_gemm(const omp_decoder_plan* P, int64_t RL, const void* A, const void* W, int K, int N, const float* bias, int bias_mod, int64_t bias_stride,
+                 const void* res, void* C, int out_dtype, int act, hipStream_t st, const float* ln_g = nullptr, const float* ln_b = nullptr) {
+  omp_gemm_args a{};
+  a.lda = K; a.W = W; a.ldw = K; a.bias = bias; a.bias_row = nullptr; a.bias_row_stride = bias_stride; a.bias_row_mod = bias_mod;
+  a.ldr = N; a.ldc = N; a.N = N; a.K = K;
+  a.dtype = P->dtype; a.out_dtype = out_dtype; a.act = act;
+  a.ln_gamma = ln_g; a.ln_beta = ln_b; a.ln_eps = P->eps; a.small_m_splitk = 1;
+  const int64_t chunk = P->R <= 64 ? 64 : RL;
+  const size_t ea = ln_g != nullptr ? 4 : 2, ec = out_dtype == OMP_F32 ? 4 : 2;
+  for (int64_t r0 = 0; r0 < RL; r0 += chunk) {
+    a.A = reinterpret_cast<const char*>(A) + r0 * K * ea;
+    a.C = reinterpret_cast<char*>(C) + r0 * N * ec;
+    a.residual = res != nullptr ? reinterpret_cast<const char*>(res) + r0 * N * ec : nullptr;
+    a.M = RL - r0 < chunk ? RL - r0 : chunk;
+    a.bias_row_off = bias_mod > 0 ? (int)(r0 % bias_mod) : 0;
+    RUN(omp_gemm_bias_act(&a, st));
+  }
+  return OMP_OK;
+}
+
+// ln_gemm of the pass (the LayerNorm output goes to pf_att, which is free between the attention kernels' outputs and their out-projections)
+int prefill_ln_gemm(const omp_decoder_plan* P, int64_t RL, const float* g, const float* b, const void* W, int N, const float* bias, int bias_mod,
+                    int64_t bias_stride, void* C, int out_dtype, int act, hipStream_t st) {
+  const int d = P->d_model;
+  if (P->R <= 64) return prefill_gemm(P, RL, P->pf_x, W, d, N, bias, bias_mod, bias_stride, nullptr, C, out_dtype, act, st, g, b);
+  RUN(omp_layernorm(P->pf_x, OMP_F32, g, b, P->pf_att, P->dtype, nullptr, RL, d, P->eps, st));
+  return prefill_gemm(P, RL, P->pf_att, W, d, N, bias, bias_mod, bias_stride, nullptr, C, out_dtype, act, st);
+}
+
+int prefill_launch(const omp_decoder_plan* P, hipStream_t st) {
+  const int d = P->d_model, R = P->R, L = P->n_prompt - 1, T = P->dtype;
+  const int64_t RL = (int64_t)R * L;
+  OMP_CHECK_ARG(P->prefill_tiles != nullptr && (int64_t)P->n_prefill_tiles * 16 * P->q_tiles >= RL,
+                "omp_decoder_run: the prefill tiles table (%d groups of at most %d rows) does not cover %lld prefill rows", P->n_prefill_tiles, 16 * P->q_tiles, (long long)RL);
+  OMP_CHECK_ARG(P->pf_rows >= RL && P->pf_x && P->pf_qkv && P->pf_att && P->pf_q && P->pf_ffh && (P->n_split == 1 || P->pf_partial),
+                "omp_decoder_run: the prefill scratch holds %lld rows, the pass needs %lld (x, qkv, att, q, ffh; partial with n_split > 1)", (long long)P->pf_rows, (long long)RL);
+  hipLaunchKernelGGL((dec_embed_ln_kernel<float, true>), dim3((unsigned)((RL + 3) / 4)), dim3(256), 0, st, P->seq, P->seq_ld, P->d_pos, P->word_emb, P->pos_tab,
+                     P->emb_g, P->emb_b, P->pf_x, (float*)nullptr, (int)RL, d, P->eps, L);
+  OMP_CHECK_LAUNCH("omp_decoder_run(prefill embedding)");
+  CrossP cp;
+  cp.q = P->pf_q; cp.ldq = d; cp.img_stride = P->kv_img_stride; cp.Mpad = P->Mpad;
+  cp.kmask = P->key_mask; cp.klen = P->key_len; cp.groups = P->prefill_tiles; cp.out = P->pf_att; cp.ldo = d;
+  cp.partial = P->pf_partial; cp.M = P->M; cp.nH = P->n_heads; cp.R = (int)RL; cp.kpw = 0; cp.lo_off = 0;
+  // the mid chain where the STEP takes it (step_launch: by the plan's rows, not the pass's)
+  bool mid_chain = omp_cur().dec_fused != 1 && d == 512 && P->n_heads == 8 && R >= 16;
+  for (int li = 0; li < P->n_layers && mid_chain; ++li) mid_chain = P->layers[li].rows_mid != nullptr;
+  omp_dec_rows_args ma{};
+  ma.R = (int)RL; ma.eps = P->eps; ma.d_pos = P->d_pos; ma.pos_mod = L; ma.x = P->pf_x; ma.att = P->pf_att; ma.q = P->pf_q;
+  for (int li = 0; li < P->n_layers; ++li) {
+    const omp_dec_layer& Ly = P->layers[li];
+    cp.K = Ly.crossK; cp.V = Ly.crossVt;
+    RUN(prefill_ln_gemm(P, RL, Ly.n1_g, Ly.n1_b, Ly.sa_in_w, 3 * d, Ly.sa_bias_tab, L, 3 * d, P->pf_qkv, T, OMP_ACT_NONE, st));
+    hipLaunchKernelGGL((dec_self_attn_kernel<bf16_t, true>), dim3((unsigned)RL, (P->n_heads + 3) / 4), dim3(256), 0, st, (const bf16_t*)P->pf_qkv, (bf16_t*)Ly.kcache,
+                       (bf16_t*)Ly.vcache, (bf16_t*)P->pf_att, P->d_pos, (int)RL, P->n_heads, d, P->Lmax, L);
+    OMP_CHECK_LAUNCH("omp_decoder_run(prefill self-attention)");
+    if (li + 1 == P->n_layers) break;   // the cache rows are all that later steps read of the last layer at these positions
+    if (mid_chain) {
+      ma.wstream = Ly.rows_mid; ma.wave_stride = Ly.rows_mid_stride; ma.out_b = Ly.sa_out_b; ma.ln_g = Ly.n2_g; ma.ln_b = Ly.n2_b; ma.qbias_tab = Ly.ca_qbias_tab;
+      RUN(omp_dec_rows_mid(&ma, st));
+    } else {
+      RUN(prefill_gemm(P, RL, P->pf_att, Ly.sa_out_w, d, d, Ly.sa_out_b, 0, 0, P->pf_x, P->pf_x, OMP_F32, OMP_ACT_NONE, st));
+      RUN(prefill_ln_gemm(P, RL, Ly.n2_g, Ly.n2_b, Ly.ca_q_w, d, Ly.ca_qbias_tab, L, d, P->pf_q, T, OMP_ACT_NONE, st));
+    }
+    RUN(launch_cross(cp, P->n_prefill_tiles, T, P->n_split, P->q_tiles, st));
+    RUN(prefill_gemm(P, RL, P->pf_att, Ly.ca_out_w, d, d, Ly.ca_out_b, 0, 0, P->pf_x, P->pf_x, OMP_F32, OMP_ACT_NONE, st));
+    RUN(prefill_ln_gemm(P, RL, Ly.n3_g, Ly.n3_b, Ly.ff1_w, P->d_ff, Ly.ff1_b, 0, 0, P->pf_ffh, T, OMP_ACT_RELU, st));
+    RUN(prefill_gemm(P, RL, P->pf_ffh, Ly.ff2_w, P->d_ff, d, Ly.ff2_b, 0, 0, P->pf_x, P->pf_x, OMP_F32, OMP_ACT_NONE, st));
+  }
+  hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, st, P->d_pos, L);
+  OMP_CHECK_LAUNCH("omp_decoder_run(prefill position)");
+  omp_cur().prefill_passes += 1;
+  return OMP_OK;
+}
+
 // sampling steps per multi-step graph; OMP355_GRAPH_RUN=1 switches the runs off (A/B): parsed strictly like the other knobs of this file
 int graph_run_steps() {
   static const SampleEnv v = strict_env_int("OMP355_GRAPH_RUN", OMP_GRAPH_RUN);
@@ -1981,6 +2089,14 @@ int sample_and_advance(const omp_decoder_plan* P, hipStream_t st) {
 }
 
 }  // namespace
+
+extern "C" int omp_debug_prefill(int mode) {
+  OMP_CHECK_ARG(mode == 0 || mode == 1, "omp_debug_prefill: 0 (the batched pass where the plan asks for it and is eligible) or 1 (stepwise prefill always), got %d", mode);
+  omp_cur().prefill = mode;
+  return OMP_OK;
+}
+
+extern "C" int64_t omp_debug_prefill_passes(void) { return omp_cur().prefill_passes; }
 
 extern "C" int omp_debug_dec_fused(int mode) {
   omp_cur().dec_fused = mode == 1 ? 1 : 0;
@@ -2053,7 +2169,12 @@ extern "C" int omp_decoder_run(const omp_decoder_plan* P, int first_pos, int n_s
                 first_pos, first_pos + n_steps, P->Lmax);
   OMP_CHECK_ARG(first_pos + n_steps + 1 <= P->seq_ld, "omp_decoder_run: seq_ld %d too small", P->seq_ld);
   hipStream_t st = (hipStream_t)s;
-  for (int i = 0; i < n_steps; ++i) {
+  int i0 = 0;
+  if (first_pos == 0 && P->prefill && n_steps >= P->n_prompt - 1 && omp_cur().prefill != 1 && prefill_eligible(P)) {
+    RUN(prefill_launch(P, st));   // positions 0 .. n_prompt - 2 in one pass; *d_pos = n_prompt - 1 behind it
+    i0 = P->n_prompt - 1;
+  }
+  for (int i = i0; i < n_steps; ++i) {
     const int pos = first_pos + i;
     const bool do_head = pos >= P->n_prompt - 1;
     if (!do_head) {

@@ -105,10 +105,13 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
   const int n = n0 + cidx * CH;
   const bool vec_path = vec_ok && n + CH <= p.N;
   const float* bias = p.bias;
-  if (bias != nullptr && p.bias_row != nullptr) bias += (int64_t)(*p.bias_row) * p.bias_row_stride;
+  // the bias table's per-row form (p.bias_row_mod > 0: row m takes table row (bias_row_off + m) % bias_row_mod): the column bias of a
+  // row is read where the row is stored; the same `+ bias` on the same accumulator as the one-row form, so a row's bits are its bits there
+  const bool bias_per_row = bias != nullptr && p.bias_row_mod > 0;
+  if (bias != nullptr && p.bias_row != nullptr && !bias_per_row) bias += (int64_t)(*p.bias_row) * p.bias_row_stride;
   // unconditional 16-byte loads (a branch here would make the compiler wait for them on the spot): threads
   // without a vector-loadable column bias read the first bytes of W instead and discard them
-  const bool bias_vec = bias != nullptr && !p.bias_m && n + CH <= p.N && (reinterpret_cast<uintptr_t>(bias) & 15) == 0;
+  const bool bias_vec = bias != nullptr && !bias_per_row && !p.bias_m && n + CH <= p.N && (reinterpret_cast<uintptr_t>(bias) & 15) == 0;
   const float* bsrc = bias_vec ? bias + n : reinterpret_cast<const float*>(p.W);
   f32x4 braw[CH / 4];
 #pragma unroll
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
   float bcol[CH];
 #pragma unroll
   for (int q = 0; q < CH; ++q) bcol[q] = bias_vec ? braw[q >> 2][q & 3] : 0.f;
-  if (bias != nullptr && !p.bias_m && !bias_vec) {   // ragged N edge
+  if (bias != nullptr && !p.bias_m && !bias_vec && !bias_per_row) {   // ragged N edge
 #pragma unroll
     for (int q = 0; q < CH; ++q)
       if (n + q < p.N) bcol[q] = bias[n + q];
@@ -264,6 +267,7 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
         const int64_t m = m0 + r;
         if (m < p.M) {
           const float bm = bias_rows ? bias[m] : 0.f;   // bias_along_m: the row's bias, as the 4-value path below adds it
+          const float* brow = bias_per_row ? bias + (int64_t)((p.bias_row_off + (int)m) % p.bias_row_mod) * p.bias_row_stride + n : nullptr;
           float v[CH];
 #pragma unroll
           for (int q = 0; q < CH; q += 4) {
@@ -272,7 +276,7 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
           }
 #pragma unroll
           for (int q = 0; q < CH; ++q) {
-            v[q] += bcol[q];
+            v[q] += bias_per_row ? brow[q] : bcol[q];
             if (bias_rows) v[q] += bm;   // a branch, not + 0: a product without bias_along_m keeps its bits (-0 + 0 = +0)
             if constexpr (decltype(ACT)::value == OMP_ACT_GELU && !std::is_same<TOut, bf16_t>::value) v[q] = gelu_erf(v[q]);
             if constexpr (decltype(ACT)::value == OMP_ACT_RELU) v[q] = fmaxf(v[q], 0.0f);
@@ -328,7 +332,11 @@ __global__ __launch_bounds__(256) void gemm_dma(GemmP p) {
       if (bias != nullptr && p.bias_m && m0 + r < p.M) bm = bias[m0 + r];
       float v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = apply_act<TOut>(t[u] + bcol[q + u] + bm, p.act);
+      for (int u = 0; u < 4; ++u) {
+        float bc = bcol[q + u];
+        if (bias_per_row && m0 + r < p.M && n + q + u < p.N) bc = bias[(int64_t)((p.bias_row_off + (int)m0 + r) % p.bias_row_mod) * p.bias_row_stride + n + q + u];
+        v[u] = apply_act<TOut>(t[u] + bc + bm, p.act);
+      }
       store4<TOut>(p, m0 + r, n + q, v);
     }
   }
@@ -528,7 +536,8 @@ __global__ __launch_bounds__(256) void gemm_small(GemmP p) {
 #pragma unroll
     for (int w = 1; w < 4; ++w) a += red[(w * MF + wave) * 64 + lane];
     const float* bias = p.bias;
-    if (bias != nullptr && p.bias_row != nullptr) bias += (int64_t)(*p.bias_row) * p.bias_row_stride;
+    if (bias != nullptr && p.bias_row_mod > 0) bias += (int64_t)((p.bias_row_off + wave * 16 + lrow) % p.bias_row_mod) * p.bias_row_stride;   // per-row form: this lane's row
+    else if (bias != nullptr && p.bias_row != nullptr) bias += (int64_t)(*p.bias_row) * p.bias_row_stride;
     epilogue_store<TOut>(p, bias, (int64_t)wave * 16 + lrow, nb + lg * 4, a);
   }
 }
@@ -719,6 +728,10 @@ int launch_gemm(const GemmP& p0, hipStream_t st) {
   if (p.store_mode == OMP_STORE_ROWSTAT) which = 5;   // the row statistics live in the 128 x 128 kernel's epilogue, whatever is forced
   else if (p.ln_g != nullptr || (which == 0 && p.small_hint && p.M <= 64 && p.K % (4 * Mma<T>::KSTEP) == 0)) which = 4;
   else if (which == 0) which = gemm_auto_select(p, BI, BO);
+  // the bias table's per-row form lives in the epilogues of gemm_small and gemm_dma: the dispatch stays with them (64 x 64 / 128 x 128 by the
+  // tile count, as gemm_auto_select cuts them; few rows without the split-K hint have no kernel for it: selector -1, refused below)
+  if (p.bias_row_mod > 0 && which != 4 && which != 5 && which != 6)
+    which = p.M <= 64 ? -1 : (ceil_div64(p.M, 128) * ceil_div64(p.N, 128) < 256 ? 6 : 5);
   const GemmSel* sel = gemm_selector(which);
   if (sel == nullptr) {
     omp_set_error("omp_gemm_bias_act: unknown kernel selector %d", which);
@@ -804,6 +817,7 @@ extern "C" int omp_gemm_bias_act(const omp_gemm_args* a, omp_stream_t s) {
   GemmP p;
   p.A = a->A; p.lda = a->lda; p.W = a->W; p.ldw = a->ldw;
   p.bias = a->bias; p.bias_row = a->bias_row; p.bias_row_stride = a->bias_row_stride;
+  p.bias_row_mod = a->bias_row_mod; p.bias_row_off = a->bias_row_off;
   p.residual = a->residual; p.ldr = a->ldr; p.C = a->C; p.ldc = a->ldc;
   p.M = a->M; p.N = a->N; p.K = a->K; p.act = a->act;
   p.trans_out = a->trans_out; p.trans_rows = a->trans_rows; p.trans_ld = a->trans_ld; p.tiles_m = p.tiles_n = 0;
@@ -836,6 +850,10 @@ extern "C" int omp_gemm_bias_act(const omp_gemm_args* a, omp_stream_t s) {
                   "omp_gemm_bias_act: blocked K/V store shape mismatch (M=%lld N=%d)", (long long)a->M, a->N);
   }
   OMP_CHECK_ARG(!p.bias_m || (a->bias_row == nullptr), "omp_gemm_bias_act: bias_along_m excludes bias_row");
+  OMP_CHECK_ARG(a->bias_row_mod >= 0 && (a->bias_row_mod == 0 || (a->bias != nullptr && a->bias_row_off >= 0 && a->bias_row_stride >= a->N && !p.bias_m &&
+                                                                    p.store_mode == OMP_STORE_PLAIN && !a->trans_out)),
+                "omp_gemm_bias_act: the per-row bias table (bias_row_mod %d) takes a bias table of rows >= N, bias_row_off >= 0, a plain row-major destination, no bias_along_m",
+                a->bias_row_mod);
   OMP_CHECK_ARG((a->ln_gamma == nullptr) == (a->ln_beta == nullptr), "omp_gemm_bias_act: ln_gamma and ln_beta go together");
   hipStream_t st = (hipStream_t)s;
   if (a->dtype == OMP_F32) return launch_gemm<float, float>(p, st);

@@ -12,6 +12,7 @@ struct GemmP {
   const void* A; int64_t lda;
   const void* W; int64_t ldw;
   const float* bias; const int32_t* bias_row; int64_t bias_row_stride;
+  int bias_row_mod, bias_row_off;                       // > 0: the table's per-row form -- row m takes table row (bias_row_off + m) % bias_row_mod (gemm_dma, gemm_small)
   const void* residual; int64_t ldr;
   void* C; int64_t ldc;
   int64_t M; int N; int K;

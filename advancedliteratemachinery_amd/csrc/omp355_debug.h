@@ -48,6 +48,8 @@ int omp_debug_gemm_choice(const omp_gemm_args* args);
 int omp_debug_set_gemm_trace(void* buffer, int64_t n_workgroups);
 int omp_debug_swin_attn_impl(int which); /* 0 = matrix-core kernel (default), 1 = scalar cross-check kernel, 2 = matrix cores with per-score table lookups */
 int omp_debug_dec_fused(int mode);       /* 0 = fused few-row decoder step kernels where they apply (default), 1 = one launch per op everywhere (A/B, cross-check) */
+int omp_debug_prefill(int mode);         /* 0 = omp_decoder_run runs the batched prompt prefill where the plan sets `prefill` and is eligible (default), 1 = the stepwise prefill always (A/B, tests) */
+int64_t omp_debug_prefill_passes(void);  /* batched prefill passes the calling thread's context has launched so far (the tests assert which path ran) */
 int omp_debug_self_attn_impl(int which); /* 0 auto, 1 = one wave per (row, head), 2 = one wave per row (all 8 heads) */
 /* The fused few-row self-attention step of the point decoder on its own (csrc/decoder.hip dec_fused_self_attn_kernel, d = 512, 8 heads, bf16),
  * through the engine's launch function: LayerNorm(x [R, 512] fp32) -> q | k | v = W [1536, 512] bf16 + bias_tab [Pmax, 1536] row *d_pos ->

@@ -122,7 +122,19 @@ class _Phase(object):
         self.vc = [e(R, Lmax, d) for _ in range(L)]
         self.plan = _lib.DecoderPlan()
         self.n_tiles = 0
+        self.pf = None               # scratch of the batched prompt prefill (prefill_scratch), allocated when a bound plan first takes it
         self.slots = OrderedDict()   # plan bytes -> graph slot (a phase re-bound to other K/V slabs is another graph)
+
+    def prefill_scratch(self, dec, rows):
+        """Buffers of the batched prompt prefill for `rows` = R * (n_prompt - 1) prefill rows (include/omp355.h omp_decoder_plan.pf_*):
+        allocated once per phase -- a phase's R, n_split and prompt length never change -- and kept, so that plan pointers stay stable."""
+        if self.pf is None or self.pf['rows'] < rows:
+            dev, T, d = dec.device, dec.dtype, dec.d
+            e = lambda *s, dtype=T: torch.empty(s, dtype=dtype, device=dev)   # noqa: E731
+            self.pf = dict(rows=rows, tiles=torch.zeros(rows + 64, 3, dtype=torch.int32, device=dev), x=e(rows, d, dtype=torch.float32),
+                           qkv=e(rows, 3 * d), att=e(rows, d), q=e(rows, d), ffh=e(rows, dec.ff),
+                           partial=e(rows, dec.nH, max(1, self.n_split), 68, dtype=torch.float32))
+        return self.pf
 
     def release_graphs(self):
         for slot, ctx in self.slots.values():
@@ -206,6 +218,9 @@ class Decoder(object):
         # (profiles/r06d_ab_xcd_split_*).  Off by default; OMP355_XCD_SPLIT=1 is the A/B knob
         self.xcd_masks = {'poly': 0x0F, 'rec': 0xF0} if env_flag('OMP355_XCD_SPLIT', False) else {}
         self._x3_cache = {}   # kind -> (layers, head) with every matrix as its [w_hi | w_hi | w_lo] image (bf16x3 engine, R > 64)
+        # point phases of the launch-per-Linear bf16 step run their prompt positions as ONE batched pass (csrc/decoder.hip: prefill_launch);
+        # OMP355_PREFILL=0: one step per prompt position (A/B)
+        self.prefill = env_flag('OMP355_PREFILL', True)
 
     GRAPH_RUN = 8       # positions per omp_decoder_run call of the two-stream polygon / recognition schedule (csrc/common.h OMP_GRAPH_RUN)
     X3_MIN_ROWS = env_int('OMP355_X3_MIN', 65, 65, 1 << 30)    # phases with more rows run their products as split-bf16 products (csrc/decoder.hip: step_launch_x3)
@@ -340,6 +355,31 @@ class Decoder(object):
             r0 += n
         return groups, qt
 
+    PREFILL_MIN_ROWS, PREFILL_MAX_ROWS = 64, 4096   # csrc/decoder.hip: prefill_eligible (plan rows from / prefill rows up to)
+
+    @staticmethod
+    def make_prefill_tiles(groups, qt, L):
+        """The cross-attention groups of the batched prompt prefill from make_tiles' groups: prefill row r * L + j is plan row r at
+        prompt position j, so the R_img * L prefill rows of an image are contiguous; they are cut into groups of <= 16 * qt rows --
+        ceil(R_img * L / (16 * qt)) slab passes per image instead of L * ceil(R_img / (16 * qt))."""
+        counts = OrderedDict()
+        for _, n, img in groups:
+            counts[img] = counts.get(img, 0) + n
+        out, r0 = [], 0
+        for img, n in counts.items():
+            rows = n * L
+            for o in range(0, rows, 16 * qt):
+                out.append((r0 + o, min(16 * qt, rows - o), img))
+            r0 += rows
+        return out
+
+    def _prefill_ok(self, ph, n_prompt, use_rows, use_x3):
+        """Plans omp_decoder_run takes the batched prompt prefill for (csrc/decoder.hip prefill_eligible decides again): point phases
+        on the launch-per-Linear bf16 step -- more rows than the fused few-row kernels take, fewer than the chains want."""
+        rows = ph.R * (n_prompt - 1)
+        return bool(self.prefill and ph.kind == 'pt' and n_prompt >= 3 and self.dtype == torch.bfloat16 and self.args.tfm_pre_norm and not use_rows
+                    and not use_x3 and not self.kv_split and self.PREFILL_MIN_ROWS <= ph.R < 1024 and rows <= self.PREFILL_MAX_ROWS)
+
     def _bind(self, ph, kv, tiles, n_prompt, suppress_eos, infer_vie):
         tiles, qt = tiles
         P, a, d = ph.plan, self.args, self.d
@@ -405,6 +445,20 @@ class Decoder(object):
         P.finished, P.lengths = ph.finished.data_ptr(), ph.lengths.data_ptr()
         for n in ('x', 'x2', 'y', 'qkv', 'att', 'q', 'ffh', 'hh0', 'hh1', 'partial', 'logits'):
             setattr(P, n, getattr(ph, n).data_ptr())
+        if self._prefill_ok(ph, n_prompt, use_rows, use_x3):
+            pf = ph.prefill_scratch(self, ph.R * (n_prompt - 1))
+            key = (tuple(tiles), qt, n_prompt)
+            if pf.get('tiles_key') != key:   # the table follows from the step's tiles: a call with the same rows per image finds it on the device
+                pt = torch.tensor(self.make_prefill_tiles(tiles, qt, n_prompt - 1), dtype=torch.int32).reshape(-1, 3)
+                pf['tiles'][:pt.shape[0]].copy_(pt.to(self.device, non_blocking=False))
+                pf['tiles_key'], pf['n_tiles'] = key, pt.shape[0]
+            P.prefill, P.n_prefill_tiles, P.prefill_tiles, P.pf_rows = 1, pf['n_tiles'], pf['tiles'].data_ptr(), pf['rows']
+            for n in ('x', 'qkv', 'att', 'q', 'ffh', 'partial'):
+                setattr(P, 'pf_' + n, pf[n].data_ptr())
+        else:
+            P.prefill, P.n_prefill_tiles, P.prefill_tiles, P.pf_rows = 0, 0, None, 0
+            for n in ('x', 'qkv', 'att', 'q', 'ffh', 'partial'):
+                setattr(P, 'pf_' + n, None)
         s = P.sample
         s.kind, s.num_bins, s.pt_eos, s.poly_eos, s.rec_eos = KIND_ID[ph.kind], a.num_bins, a.pt_eos_index, a.poly_eos_index, a.rec_eos_index
         s.vocab, s.vie_categories, s.infer_vie = self.V, a.vie_categories, 1 if infer_vie else 0

@@ -17,6 +17,8 @@ error message, not a silently different engine.  Knobs that change a
                        phase 98 -> 109 ms: the other decoder's cross-attention is left with four XCDs' share of the fabric; profiles/r06d_*)
   OMP355_X3_MIN        bf16x3 engine: rows from which a decoder phase runs its products as split-bf16 GEMMs (default 65; 161 puts the 160-row point phase
                        on the fp32 few-row kernels: measured slower, profiles/r06y_*)
+  OMP355_PREFILL       point phases of 64+ rows on the bf16 engine: the prompt positions as ONE batched pass over the memory (1, default) or one step per
+                       position (0; A/B -- the same bits either way.  Inside one process the tests switch with omp_debug_prefill instead)
   OMP355_DEC_PRIORITY  pipeline lanes: decoder streams at high priority (0 / 1, default 0)
 Read in C (csrc/decoder.hip), parsed strictly there -- anything but a non-negative integer fails every omp_decoder_run:
   OMP355_SAMPLE_BLOCK_MAX_ROWS  rows up to which sampling runs a workgroup per row (default 1024)

@@ -66,7 +66,9 @@ int omp_layernorm_sampled(const void* x, int x_dtype, const float* gamma, const 
  * omniparser.py:31 (input_proj), transformer.py:448 (linear1/2) and the in/out projections of
  * nn.MultiheadAttention (transformer.py:386-387), block/mlp.py:11-13 (prediction heads).
  * bias_row (device int32, optional) selects row *bias_row of a [rows, bias_row_stride] bias table
- * (used for the per-position query/key bias of the decoders).
+ * (used for the per-position query/key bias of the decoders).  bias_row_mod > 0 is the table's PER-ROW form:
+ * row m takes table row (bias_row_off + m) % bias_row_mod and bias_row is not read (the batched prompt prefill of
+ * omp_decoder_run, whose row r * L + j sits at position j).
  * trans_out: store C transposed per batch of `trans_rows` consecutive rows:
  *   C[(m / trans_rows) * N * trans_ld + n * trans_ld + (m % trans_rows)]   (ldc ignored). */
 typedef struct {
@@ -124,6 +126,10 @@ typedef struct {
    * dropped).  With swapped operands (OMP_STORE_VBLK) the weight is the [hi | lo] side and the activation arrives as
    * [hi | hi | lo] (omp_split_bf16, triple = 1).  0 = plain product. */
   int32_t a_wrap;
+  /* per-row form of the bias table (see above): plain row-major destinations without bias_along_m; honoured by the 64 x 64 and
+   * 128 x 128 tile kernels and by the split-K small-M kernel, and the dispatch stays with them (a row's bits are the same on all
+   * three tile sizes, so a row computed here equals the row a step computes with bias_row).  0 = off. */
+  int32_t bias_row_mod, bias_row_off;
 } omp_gemm_args;
 int omp_gemm_bias_act(const omp_gemm_args* a, omp_stream_t s);
 
@@ -409,10 +415,32 @@ typedef struct {
   float* partial;
   float* logits; /* [R,vocab] */
   omp_sample_cfg sample;
+  /* Batched prompt prefill (the members behind `sample`).  The prompt tokens are known before the first launch, and all that positions 0 .. n_prompt - 2
+   * leave behind is the self-attention K / V cache rows of those positions.  With prefill != 0 an ELIGIBLE plan runs them as ONE pass
+   * over L = n_prompt - 1 positions when omp_decoder_run starts at first_pos == 0 with n_steps >= L: R * L prefill rows, row r * L + j
+   * = plan row r at position j; every layer but the last in full, the last one up to its self-attention's cache append; no head, no
+   * sampling; *d_pos = L afterwards, the ticket word untouched.  Cross-attention streams an image's K / V^T slabs once per group of
+   * prefill_tiles -- ceil(R_img * L / (16 * q_tiles)) passes per image instead of L * ceil(R_img / (16 * q_tiles)) -- with the
+   * plan's own q_tiles and n_split, i.e. the step's kernel, key ranges and merge.  Every row runs the operations of the stepwise
+   * prefill in the same order: caches, ids and probabilities are the same bits.
+   * Eligible: dtype OMP_BF16, pre_norm, no rows_fused / gemm_x3 / kv_split, n_prompt >= 3, 64 <= R < 1024 (the launch-per-Linear step
+   * with one self-attention wave per (row, head)), R * L <= 4096, no forced GEMM kernel, not the fused few-row step.  Every other plan
+   * runs the stepwise prefill whatever `prefill` says.  An eligible plan with prefill set and a table or scratch too small is refused. */
+  int32_t prefill;               /* switch: 0 = stepwise prefill */
+  int32_t n_prefill_tiles;       /* groups in prefill_tiles */
+  const int32_t* prefill_tiles;  /* {row0, nrows <= 16 * q_tiles, image} over the R * L prefill rows: an image's R_img * L rows are contiguous */
+  int64_t pf_rows;               /* rows each pf_* buffer holds, >= R * L */
+  float* pf_x;                   /* [pf_rows, d] fp32 */
+  void* pf_qkv;                  /* [pf_rows, 3d] */
+  void* pf_att;                  /* [pf_rows, d] (also holds the LayerNorm outputs between its uses) */
+  void* pf_q;                    /* [pf_rows, d] */
+  void* pf_ffh;                  /* [pf_rows, d_ff] */
+  float* pf_partial;             /* fp32 [pf_rows][n_heads][n_split][68] (n_split > 1) */
 } omp_decoder_plan;
 
 /* Runs steps for input positions first_pos .. first_pos+n_steps-1 (host-side counter must match
- * *d_pos).  Positions < n_prompt-1 are prompt prefill (no head / sampling).  graph_slot >= 0
+ * *d_pos).  Positions < n_prompt-1 are prompt prefill (no head / sampling): one eager step each, or -- omp_decoder_plan.prefill --
+ * one batched pass for all of them.  graph_slot >= 0
  * caches a hipGraph of the sampling step under that slot (call omp_decoder_graph_reset when the
  * plan's pointers or shapes change); graph_slot < 0 launches eagerly. */
 int omp_decoder_run(const omp_decoder_plan* plan, int first_pos, int n_steps, int graph_slot,
@@ -490,6 +518,8 @@ typedef struct {
    * workgroup owns 48 rows. */
   int32_t x3;
   int32_t xcd_mask;                /* XCDs whose CUs may run the launch's workgroups (omp_decoder_plan.rows_xcd_mask); 0 = all */
+  int32_t pos_mod;                 /* omp_dec_rows_mid, bf16 chains: > 0 = row r sits at position r % pos_mod and d_pos is not read (the batched prompt
+                                      prefill of omp_decoder_run); 0 = every row at *d_pos */
 } omp_dec_rows_args;
 int omp_dec_rows_mid(const omp_dec_rows_args* a, omp_stream_t s);
 int omp_dec_rows_ffn(const omp_dec_rows_args* a, omp_stream_t s);
