@@ -26,7 +26,7 @@
 // A job out of range (a page or query index that is not there, a page above 65535 characters, a query outside 1 .. 64, a range outside
 // the pool, k outside 0 .. m - 1) is REFUSED on the device: n_hits = -1, best and hits -1, and nothing outside the pool is read.
 // Nothing is allocated and nothing synchronises: pool, tables, scratch and outputs are the caller's.
-#include "common.h"
+#include "myers.h"
 
 namespace {
 
@@ -44,24 +44,8 @@ constexpr int PS_TEXT_BYTES = PS_STAGE + 4 * (PS_STAGE / PS_CHUNK + 1);
 
 static_assert(PS_BEFORE >= 2 * PS_QUERY_MAX && PS_TEXT_BYTES >= PS_STAGE + 4 * ((PS_STAGE - 1) / PS_CHUNK) && PS_HITS_MAX <= 64, "page_search layout");
 
-typedef unsigned long long u64;
-
 // where staged character `rel` (0 = PS_BEFORE characters before the round's first chunk) lives in LDS
 __device__ __forceinline__ int ps_at(int rel) { return rel + 4 * (rel / PS_CHUNK); }
-
-// one column of Myers' recurrence; `carry` is the horizontal difference of row 0: 0 for the search, 1 for the anchored distance
-__device__ __forceinline__ int ps_step(u64 Eq, u64& Pv, u64& Mv, int top, u64 carry) {
-  const u64 Xv = Eq | Mv;
-  const u64 Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-  u64 Ph = Mv | ~(Xh | Pv);
-  u64 Mh = Pv & Xh;
-  const int d = (int)((Ph >> top) & 1ull) - (int)((Mh >> top) & 1ull);
-  Ph = (Ph << 1) | carry;
-  Mh <<= 1;
-  Pv = Mh | ~(Xv | Ph);
-  Mv = Ph & Xv;
-  return d;
-}
 
 __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restrict__ pool, int64_t pool_bytes, const int32_t* __restrict__ page_off,
                                                          const int32_t* __restrict__ page_len, int n_pages, const int32_t* __restrict__ query_off,
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restri
       eqn = i < imax ? eq_of(j + 1) : 0ull;
       s2 = s1;
       s1 = s0;
-      if (j >= 1 && j <= n) s0 += ps_step(eq, Pv, Mv, top, 0);
+      if (j >= 1 && j <= n) s0 += myers_step(eq, Pv, Mv, top, 0);
       const int e = j - 1;                                 // the column that can be judged now
       if (i >= 2 && e <= n) {                              // e is one of this lane's own columns
         const u64 ke = ((u64)s1 << 32) | (u64)e;
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restri
         ++l;
         const int c = text[ps_at(end - l - r0 + PS_BEFORE)];
         const u64 Eq = __brevll(peq[min(c, sigma)]) >> (64 - m);
-        score += ps_step(Eq, rPv, rMv, top, 1);
+        score += myers_step(Eq, rPv, rMv, top, 1);
       }
       jhits[3 * lane] = end;
       jhits[3 * lane + 1] = dist;

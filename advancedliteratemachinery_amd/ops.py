@@ -885,7 +885,7 @@ def split_match_ints(ints, n, n_groups, n_thr):
     return ints[:c].reshape(n_groups, n_thr, 4), ints[c:c + n], ints[c + n:c + 2 * n]
 
 
-PAGE_TEXT_SLICE_BYTES = 32768   # omp_page_edit_distance: scratch per pair (csrc/page_text.hip: PT_SLICE_BYTES)
+PAGE_TEXT_SLICE_BYTES = 32768   # omp_page_edit_distance: scratch per pair (csrc/myers.h: PT_SLICE_BYTES)
 
 
 def page_scratch_bytes(n_pairs):
@@ -916,7 +916,7 @@ def page_edit_distance(pool, pool_bytes, a_off, a_len, b_off, b_len, sigma, scra
     return dist[:P]
 
 
-PAGE_ALIGN_CARRY_BYTES = 32768  # omp_page_align: the head of a pair's scratch (csrc/page_align.hip: PA_CARRY_BYTES)
+PAGE_ALIGN_CARRY_BYTES = 32768  # omp_page_align: the head of a pair's scratch (csrc/page_align.hip: PA_CARRY_BYTES == csrc/myers.h: PT_SLICE_BYTES)
 PAGE_ALIGN_CELL_BYTES = 16      # omp_page_align: the record of one (64-row block, text column) (csrc/page_align.hip: PA_CELL_BYTES)
 
 

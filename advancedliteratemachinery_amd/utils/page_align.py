@@ -22,7 +22,7 @@ Stage       PageAligner: one packed upload, one omp_page_align launch per chunk 
 """
 import numpy as np
 
-from .page_text import LEN_MAX, NONE, SIGMA_MAX, _check_pairs
+from .page_text import LEN_MAX, NONE, _check_pairs, _check_sigma, _DeviceStage, _rows
 
 SCRATCH_CAP = 1 << 30           # device scratch per chunk of pairs
 MAPS_CAP = (1 << 31) - 1        # map entries per chunk
@@ -43,20 +43,9 @@ def table_cpu(a, b):
         raise ValueError('a sequence holds %d codes; the limit is %d' % (max(a.size, b.size), LEN_MAX))
     if a.size > b.size:
         return np.ascontiguousarray(table_cpu(b, a).T)
-    ar = np.arange(b.size + 1, dtype=np.int32)
     D = np.empty((a.size + 1, b.size + 1), dtype=np.int32)
-    D[0] = ar
-    b_none = b == NONE
-    rows = {NONE: np.ones(b.size, dtype=np.int32)}
-    new = np.empty(b.size + 1, dtype=np.int32)
-    for i, ai in enumerate(a.tolist(), 1):
-        differs = rows.get(ai)
-        if differs is None:
-            differs = rows[ai] = ((b != ai) | b_none).astype(np.int32)
-        prev = D[i - 1]
-        new[0] = i
-        np.minimum(prev[1:] + 1, prev[:-1] + differs, out=new[1:])
-        D[i] = np.minimum.accumulate(new - ar) + ar
+    for i, row in enumerate(_rows(a, b)):
+        D[i] = row
     return D
 
 
@@ -225,22 +214,15 @@ def split_maps(res, a_len, b_len, p):
 # ---------------------------------------------------------------------------------------------
 # the device stage
 # ---------------------------------------------------------------------------------------------
-class PageAligner(object):
+class PageAligner(_DeviceStage):
     """pairs_align_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_align launch per chunk of
     pairs (a chunk's scratch stays at or below scratch_cap and its maps below 2^31 entries; the scratch is cached and grown), and ONE
     download of the counts and the maps.  A pair that alone needs more than scratch_cap raises ValueError.  There is no CPU fallback:
     HostPageAligner is the specification."""
+    HOST = 'HostPageAligner'
 
     def __init__(self, device, scratch_cap=SCRATCH_CAP):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('PageAligner runs on MI355X only (got device %s); there is no CPU fallback -- '
-                               'HostPageAligner is the host specification' % (self.device,))
-        self.scratch_cap = int(scratch_cap)
-        self.scratch = None
-        self.chunks = 0             # chunks of the last run
-        self.calls = 0
+        super().__init__(device, scratch_cap)
 
     def run(self, pool, a_off, a_len, b_off, b_len, sigma):
         """pool uint8, a_off / a_len / b_off / b_len int32 [P] as encode_pairs gives them -> dict(counts int32 [P, 4], map_off int64 [P],
@@ -249,11 +231,7 @@ class PageAligner(object):
 
         from .. import ops
         pool, a_off, a_len, b_off, b_len = _check_pairs(pool, a_off, a_len, b_off, b_len)
-        sigma = int(sigma)
-        if sigma < 0 or sigma > SIGMA_MAX:
-            raise ValueError('sigma must be 0 .. %d, got %d' % (SIGMA_MAX, sigma))
-        if pool.size and int((pool + np.uint8(1)).max()) > sigma:            # uint8 wraps: 255 -> 0, a code c -> c + 1 <= sigma
-            raise ValueError('the pool holds a code at or above sigma (%d) that is not %d' % (sigma, NONE))
+        sigma = _check_sigma(pool, sigma)
         P = a_len.size
         parts = chunk_pairs(a_len, b_len, self.scratch_cap)
         self.calls += 1
@@ -270,21 +248,14 @@ class PageAligner(object):
             rel_off[lo:hi] = map_off[lo:hi] - map_off[lo]
         most = max(int(scratch_off[hi - 1] + need[hi - 1]) for lo, hi in parts)
         with torch.cuda.device(self.device):
-            # the one upload: the int64 tables first (8-byte aligned), then the int32 tables, then the pool
-            blob = torch.from_numpy(np.concatenate([t.view(np.uint8) for t in (rel_off, scratch_off, a_off, a_len, b_off, b_len)] +
-                                                   [pool, np.zeros(1, np.uint8)])).to(self.device)
-            longs = blob[:16 * P].view(torch.int64)
-            ints = blob[16 * P:32 * P].view(torch.int32)
-            d_pool = blob[32 * P:]
-            if self.scratch is None or self.scratch.numel() < most:
-                self.scratch = None                                          # let go of the old one before the larger one is made
-                self.scratch = torch.empty(most, dtype=torch.uint8, device=self.device)
+            (d_rel, d_so, d_ao, d_al, d_bo, d_bl), d_pool = self._upload((rel_off, scratch_off, a_off, a_len, b_off, b_len), pool)
+            scratch = self._grow(most)
             out = torch.empty(4 * P + max(total, 1), dtype=torch.int32, device=self.device)
             for lo, hi in parts:
                 m0 = 4 * P + int(map_off[lo])
                 m1 = 4 * P + (int(map_off[hi]) if hi < P else total)
-                ops.page_align(d_pool, pool.size, ints[lo:hi], ints[P + lo:P + hi], ints[2 * P + lo:2 * P + hi], ints[3 * P + lo:3 * P + hi],
-                               longs[lo:hi], longs[P + lo:P + hi], sigma, self.scratch, out[m0:max(m1, m0 + 1)], m1 - m0, counts=out[4 * lo:4 * hi])
+                ops.page_align(d_pool, pool.size, d_ao[lo:hi], d_al[lo:hi], d_bo[lo:hi], d_bl[lo:hi], d_rel[lo:hi], d_so[lo:hi], sigma, scratch,
+                               out[m0:max(m1, m0 + 1)], m1 - m0, counts=out[4 * lo:4 * hi])
             host = out.cpu().numpy()                                          # the one download
         counts = host[:4 * P].reshape(P, 4)
         if (counts < 0).any():

@@ -21,7 +21,7 @@ Lengths     a page 0 .. 65535 characters, a query 1 .. 64, 0 <= k <= m - 1, 1 ..
 """
 import numpy as np
 
-from .page_text import LEN_MAX, NONE, SIGMA_MAX
+from .page_text import LEN_MAX, NONE, SIGMA_MAX, _DeviceStage, _encode, _rows
 
 QUERY_MAX = 64                  # characters a query (csrc/page_search.hip: PS_QUERY_MAX): one 64-bit word of Myers' column
 CHUNK = 128                     # text columns per lane (csrc/page_search.hip: PS_CHUNK)
@@ -94,31 +94,8 @@ def encode_search(page_texts, queries):
     for t in page_texts:
         if len(t) > LEN_MAX:
             raise ValueError('a page text holds %d characters; the limit is %d' % (len(t), LEN_MAX))
-    table = {}
-    for q in queries:
-        for ch in q:
-            table.setdefault(ch, len(table))
-    sigma = len(table)
-    if sigma > SIGMA_MAX:
-        raise ValueError('the queries hold %d distinct characters; a call takes %d' % (sigma, SIGMA_MAX))
-    chunks, total = [], 0
-
-    def place(strings, seen):
-        nonlocal total
-        off, ln = [], []
-        for s in strings:
-            if s not in seen:
-                seen[s] = total
-                chunks.append(np.fromiter((table.get(ch, NONE) for ch in s), dtype=np.uint8, count=len(s)))
-                total += len(s)
-            off.append(seen[s])
-            ln.append(len(s))
-        return np.asarray(off, dtype=np.int32).reshape(-1), np.asarray(ln, dtype=np.int32).reshape(-1)
-    page_off, page_len = place(page_texts, {})
-    query_off, query_len = place(queries, {})
-    if total > 0x7fffffff:
-        raise ValueError('the strings of a call hold %d characters; a pool takes 2^31 - 1' % total)
-    pool = np.concatenate(chunks + [np.zeros(0, np.uint8)]).astype(np.uint8)
+    pool, ((page_off, page_len), (query_off, query_len)), sigma = _encode(
+        queries, page_texts, queries, too_many='the queries hold %d distinct characters; a call takes %d')
     return pool, page_off, page_len, query_off, query_len, sigma
 
 
@@ -143,27 +120,16 @@ def row_py(q, t):
 
 
 def row_cpu(q, t, anchored=False):
-    """v_0 .. v_n of Sellers' table, int32 [n + 1]: by rows of the query, vectorised over the text; the left dependency is
-    minimum.accumulate(new - arange) + arange, as in page_text.distance_cpu.  anchored: row 0 is 0, 1, 2, ... (the plain edit distance
-    of q against every prefix of t) instead of zeros."""
+    """v_0 .. v_n of Sellers' table, int32 [n + 1]: by rows of the query, vectorised over the text (page_text._rows, the recurrence of
+    page_text.distance_cpu).  anchored: row 0 is 0, 1, 2, ... (the plain edit distance of q against every prefix of t) instead of zeros."""
     q, t = np.asarray(q, dtype=np.uint8).reshape(-1), np.asarray(t, dtype=np.uint8).reshape(-1)
     if not 1 <= q.size <= QUERY_MAX:
         raise ValueError('a query takes 1 .. %d codes, got %d' % (QUERY_MAX, q.size))
     if t.size > LEN_MAX:
         raise ValueError('a text holds %d codes; the limit is %d' % (t.size, LEN_MAX))
-    ar = np.arange(t.size + 1, dtype=np.int32)
-    prev = ar.copy() if anchored else np.zeros(t.size + 1, dtype=np.int32)
-    t_none = t == NONE
-    rows = {NONE: np.ones(t.size, dtype=np.int32)}
-    for i, qi in enumerate(q.tolist(), 1):
-        differs = rows.get(qi)
-        if differs is None:
-            differs = rows[qi] = ((t != qi) | t_none).astype(np.int32)
-        new = np.empty(t.size + 1, dtype=np.int32)
-        new[0] = i
-        np.minimum(prev[1:] + 1, prev[:-1] + differs, out=new[1:])
-        prev = np.minimum.accumulate(new - ar) + ar
-    return prev
+    for row in _rows(q, t, None if anchored else np.zeros(t.size + 1, dtype=np.int32)):
+        pass
+    return row
 
 
 def hit_ends(v, k):
@@ -266,22 +232,15 @@ class HostSearcher(object):
 # ---------------------------------------------------------------------------------------------
 # the device stage
 # ---------------------------------------------------------------------------------------------
-class PageSearcher(object):
+class PageSearcher(_DeviceStage):
     """search_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_search launch per chunk of jobs
     (a chunk's scratch stays at or below scratch_cap; the scratch is cached and grown), and ONE download of best, n_hits and hits.
     There is no CPU fallback: HostSearcher is the specification."""
+    HOST = 'HostSearcher'
 
     def __init__(self, device, scratch_cap=SCRATCH_CAP):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('PageSearcher runs on MI355X only (got device %s); there is no CPU fallback -- '
-                               'HostSearcher is the host specification' % (self.device,))
-        self.scratch_cap = int(scratch_cap)
+        super().__init__(device, scratch_cap)
         chunk_jobs(1, 1, self.scratch_cap)       # the cap holds one job that keeps one hit; run() checks it against its max_hits
-        self.scratch = None
-        self.chunks = 0             # chunks of the last run
-        self.calls = 0
 
     def run(self, pool, page_off, page_len, query_off, query_len, jobs, k, max_hits, sigma=None):
         """the inputs of search_cpu (sigma: the number of dense codes; None: the largest code of the pool below 255, plus one) -> the
@@ -302,19 +261,11 @@ class PageSearcher(object):
         if J == 0:
             return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
         with torch.cuda.device(self.device):
-            # the one upload: the int32 tables first (4-byte aligned), then the pool
-            tabs = (po, pl, qo, ql, k, jobs.reshape(-1))
-            blob = torch.from_numpy(np.concatenate([t.view(np.uint8) for t in tabs] + [pool, np.zeros(1, np.uint8)])).to(self.device)
-            n_int = sum(t.size for t in tabs)
-            ints = blob[:4 * n_int].view(torch.int32)
-            d_pool = blob[4 * n_int:]
-            d_po, d_pl, d_qo, d_ql, d_k, d_jobs = torch.split(ints, [t.size for t in tabs])
-            need = ops.page_search_scratch_bytes(max(hi - lo for lo, hi in parts), H)
-            if self.scratch is None or self.scratch.numel() < need:
-                self.scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            (d_po, d_pl, d_qo, d_ql, d_k, d_jobs), d_pool = self._upload((po, pl, qo, ql, k, jobs.reshape(-1)), pool)
+            scratch = self._grow(ops.page_search_scratch_bytes(max(hi - lo for lo, hi in parts), H))
             out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
             for lo, hi in parts:
-                ops.page_search(d_pool, pool.size, d_po, d_pl, d_qo, d_ql, d_k, d_jobs[2 * lo:2 * hi], sigma, H, self.scratch,
+                ops.page_search(d_pool, pool.size, d_po, d_pl, d_qo, d_ql, d_k, d_jobs[2 * lo:2 * hi], sigma, H, scratch,
                                 best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
             host = out.cpu().numpy()                                          # the one download
         res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))

@@ -20,7 +20,7 @@ Scores      page_scores(): per pair 1 - d / max(la, lb) in float64; mean (the re
 """
 import numpy as np
 
-LEN_MAX = 65535                 # characters a side (csrc/page_text.hip: PT_LEN_MAX)
+LEN_MAX = 65535                 # characters a side (csrc/myers.h: PT_LEN_MAX, and PT_BLOCK .. PT_NONE below)
 BLOCK = 64                      # pattern characters per lane
 STRIPE = 4096                   # pattern characters per pass over the text
 SIGMA_MAX = 254
@@ -55,6 +55,32 @@ def page_string(records, field='rec', strip=' \n', normalise=str.casefold):
     return normalise(s) if normalise is not None else s
 
 
+def _encode(code_strings, *sides, too_many):
+    """the codes of a call: the characters of `code_strings` get the dense codes 0 .. sigma - 1 in the order they first occur, every
+    other character NONE; each of `sides` (a list of strings) is placed in ONE pool, equal strings of one side sharing one range
+    -> (pool uint8, [(off, len) int32 per side], sigma).  too_many: the message for more than SIGMA_MAX distinct characters."""
+    table = {}
+    for s in code_strings:
+        for ch in s:
+            table.setdefault(ch, len(table))
+    sigma = len(table)
+    if sigma > SIGMA_MAX:
+        raise ValueError(too_many % (sigma, SIGMA_MAX))
+    chunks, total, placed = [], 0, []
+    for strings in sides:
+        seen, off = {}, []
+        for s in strings:
+            if s not in seen:
+                seen[s] = total
+                chunks.append(np.fromiter((table.get(ch, NONE) for ch in s), dtype=np.uint8, count=len(s)))
+                total += len(s)
+            off.append(seen[s])
+        placed.append((np.asarray(off, dtype=np.int32).reshape(-1), np.asarray([len(s) for s in strings], dtype=np.int32).reshape(-1)))
+    if total > 0x7fffffff:
+        raise ValueError('the strings of a call hold %d characters; a pool takes 2^31 - 1' % total)
+    return np.concatenate(chunks + [np.zeros(0, np.uint8)]).astype(np.uint8), placed, sigma
+
+
 def encode_pairs(pred_strings, gt_strings):
     """P prediction strings against P ground-truth strings -> (pool uint8, a_off, a_len, b_off, b_len int32 [P], sigma): pair p is
     pool[a_off[p] : a_off[p] + a_len[p]] (the prediction) against pool[b_off[p] : ...] (the ground truth).  Equal strings of one side
@@ -65,45 +91,18 @@ def encode_pairs(pred_strings, gt_strings):
     for s in pred_strings + gt_strings:
         if len(s) > LEN_MAX:
             raise ValueError('a page string holds %d characters; the limit is %d' % (len(s), LEN_MAX))
-    table = {}
-    for s in pred_strings:
-        for ch in s:
-            table.setdefault(ch, len(table))
-    sigma = len(table)
-    if sigma > SIGMA_MAX:
-        raise ValueError('the prediction strings hold %d distinct characters; a call takes %d -- score such pages on the host with '
-                         'utils.lexicon.edit_distance_cpu' % (sigma, SIGMA_MAX))
-    chunks, total = [], 0
-
-    def place(strings, seen):
-        nonlocal total
-        off, ln = [], []
-        for s in strings:
-            if s not in seen:
-                seen[s] = total
-                chunks.append(np.fromiter((table.get(ch, NONE) for ch in s), dtype=np.uint8, count=len(s)))
-                total += len(s)
-            off.append(seen[s])
-            ln.append(len(s))
-        return np.asarray(off, dtype=np.int32).reshape(-1), np.asarray(ln, dtype=np.int32).reshape(-1)
-    a_off, a_len = place(pred_strings, {})
-    b_off, b_len = place(gt_strings, {})
-    if total > 0x7fffffff:
-        raise ValueError('the strings of a call hold %d characters; a pool takes 2^31 - 1' % total)
-    pool = np.concatenate(chunks + [np.zeros(0, np.uint8)]).astype(np.uint8)
+    pool, ((a_off, a_len), (b_off, b_len)), sigma = _encode(
+        pred_strings, pred_strings, gt_strings, too_many='the prediction strings hold %d distinct characters; a call takes %d -- score '
+        'such pages on the host with utils.lexicon.edit_distance_cpu')
     return pool, a_off, a_len, b_off, b_len, sigma
 
 
-def distance_cpu(a, b):
-    """the Levenshtein distance of two code sequences (uint8; 255 equals nothing, itself included): the definition.  The table is walked
-    by rows of the shorter sequence, vectorised over the longer (the distance is symmetric)."""
-    a, b = np.asarray(a, dtype=np.uint8).reshape(-1), np.asarray(b, dtype=np.uint8).reshape(-1)
-    if a.size > LEN_MAX or b.size > LEN_MAX:
-        raise ValueError('a sequence holds %d codes; the limit is %d' % (max(a.size, b.size), LEN_MAX))
-    if a.size > b.size:
-        a, b = b, a
+def _rows(a, b, first=None):
+    """rows 0 .. la of the edit-distance table of the code sequences a (rows) and b (columns), int32 [lb + 1] each: THE row recurrence
+    (the module docstring's).  first: row 0 (None: 0, 1, 2, ..., the Levenshtein table); column 0 is 0, 1, 2, ... either way."""
     ar = np.arange(b.size + 1, dtype=np.int32)
-    prev = ar.copy()
+    prev = ar if first is None else first
+    yield prev
     b_none = b == NONE
     rows = {NONE: np.ones(b.size, dtype=np.int32)}                            # a_i != b, per code of a: computed once
     for i, ai in enumerate(a.tolist(), 1):
@@ -114,7 +113,20 @@ def distance_cpu(a, b):
         new[0] = i
         np.minimum(prev[1:] + 1, prev[:-1] + differs, out=new[1:])
         prev = np.minimum.accumulate(new - ar) + ar
-    return int(prev[-1])
+        yield prev
+
+
+def distance_cpu(a, b):
+    """the Levenshtein distance of two code sequences (uint8; 255 equals nothing, itself included): the definition.  The table is walked
+    by rows of the shorter sequence, vectorised over the longer (the distance is symmetric)."""
+    a, b = np.asarray(a, dtype=np.uint8).reshape(-1), np.asarray(b, dtype=np.uint8).reshape(-1)
+    if a.size > LEN_MAX or b.size > LEN_MAX:
+        raise ValueError('a sequence holds %d codes; the limit is %d' % (max(a.size, b.size), LEN_MAX))
+    if a.size > b.size:
+        a, b = b, a
+    for row in _rows(a, b):
+        pass
+    return int(row[-1])
 
 
 def _check_pairs(pool, a_off, a_len, b_off, b_len):
@@ -184,22 +196,58 @@ class HostPageScorer(object):
 # ---------------------------------------------------------------------------------------------
 # the device stage
 # ---------------------------------------------------------------------------------------------
-class PageTextScorer(object):
-    """pairs_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_edit_distance launch per chunk of
-    pairs (a chunk's scratch stays at or below scratch_cap; the scratch is cached and grown), and ONE download of the distances.
-    There is no CPU fallback: HostPageScorer is the specification."""
+def _check_sigma(pool, sigma):
+    """sigma as an int in 0 .. SIGMA_MAX with every code of the pool below it or NONE"""
+    sigma = int(sigma)
+    if sigma < 0 or sigma > SIGMA_MAX:
+        raise ValueError('sigma must be 0 .. %d, got %d' % (SIGMA_MAX, sigma))
+    if pool.size and int((pool + np.uint8(1)).max()) > sigma:                # uint8 wraps: 255 -> 0, a code c -> c + 1 <= sigma
+        raise ValueError('the pool holds a code at or above sigma (%d) that is not %d' % (sigma, NONE))
+    return sigma
 
-    def __init__(self, device, scratch_cap=SCRATCH_CAP):
+
+class _DeviceStage(object):
+    """what PageTextScorer, page_search.PageSearcher and page_align.PageAligner share: the device check, the cached scratch and the
+    packed upload.  HOST names the host twin, the specification."""
+    HOST = None
+
+    def __init__(self, device, scratch_cap):
         import torch
         self.device = torch.device(device)
         if self.device.type != 'cuda':
-            raise RuntimeError('PageTextScorer runs on MI355X only (got device %s); there is no CPU fallback -- '
-                               'HostPageScorer is the host specification' % (self.device,))
+            raise RuntimeError('%s runs on MI355X only (got device %s); there is no CPU fallback -- '
+                               '%s is the host specification' % (type(self).__name__, self.device, self.HOST))
         self.scratch_cap = int(scratch_cap)
-        chunk_pairs(1, self.scratch_cap)
         self.scratch = None
         self.chunks = 0             # chunks of the last run
         self.calls = 0
+
+    def _grow(self, need):
+        """the cached scratch, at least `need` bytes"""
+        import torch
+        if self.scratch is None or self.scratch.numel() < need:
+            self.scratch = None                                              # let go of the old one before the larger one is made
+            self.scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.scratch
+
+    def _upload(self, tables, pool):
+        """the one upload: the tables, the widest first (each lands on a multiple of its own width), then the pool -> (the tables as
+        device tensors of their own types, the pool)"""
+        import torch
+        blob = torch.from_numpy(np.concatenate([t.view(np.uint8) for t in tables] + [pool, np.zeros(1, np.uint8)])).to(self.device)
+        ends = np.cumsum([t.nbytes for t in tables]).tolist()
+        return [blob[e - t.nbytes:e].view(getattr(torch, t.dtype.name)) for t, e in zip(tables, ends)], blob[ends[-1]:]
+
+
+class PageTextScorer(_DeviceStage):
+    """pairs_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_edit_distance launch per chunk of
+    pairs (a chunk's scratch stays at or below scratch_cap; the scratch is cached and grown), and ONE download of the distances.
+    There is no CPU fallback: HostPageScorer is the specification."""
+    HOST = 'HostPageScorer'
+
+    def __init__(self, device, scratch_cap=SCRATCH_CAP):
+        super().__init__(device, scratch_cap)
+        chunk_pairs(1, self.scratch_cap)
 
     def run(self, pool, a_off, a_len, b_off, b_len, sigma):
         """pool uint8, a_off / a_len / b_off / b_len int32 [P] as encode_pairs gives them -> int32 [P] as numpy"""
@@ -207,11 +255,7 @@ class PageTextScorer(object):
 
         from .. import ops
         pool, a_off, a_len, b_off, b_len = _check_pairs(pool, a_off, a_len, b_off, b_len)
-        sigma = int(sigma)
-        if sigma < 0 or sigma > SIGMA_MAX:
-            raise ValueError('sigma must be 0 .. %d, got %d' % (SIGMA_MAX, sigma))
-        if pool.size and int((pool + np.uint8(1)).max()) > sigma:            # uint8 wraps: 255 -> 0, a code c -> c + 1 <= sigma
-            raise ValueError('the pool holds a code at or above sigma (%d) that is not %d' % (sigma, NONE))
+        sigma = _check_sigma(pool, sigma)
         P = a_len.size
         self.calls += 1
         parts = chunk_pairs(P, self.scratch_cap)
@@ -219,17 +263,11 @@ class PageTextScorer(object):
         if P == 0:
             return np.zeros(0, dtype=np.int32)
         with torch.cuda.device(self.device):
-            # the one upload: the int32 tables first (4-byte aligned), then the pool
-            blob = torch.from_numpy(np.concatenate([t.view(np.uint8) for t in (a_off, a_len, b_off, b_len)] + [pool, np.zeros(1, np.uint8)])).to(self.device)
-            ints = blob[:16 * P].view(torch.int32)
-            d_pool = blob[16 * P:]
-            need = ops.page_scratch_bytes(max(hi - lo for lo, hi in parts))
-            if self.scratch is None or self.scratch.numel() < need:
-                self.scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            (d_ao, d_al, d_bo, d_bl), d_pool = self._upload((a_off, a_len, b_off, b_len), pool)
+            scratch = self._grow(ops.page_scratch_bytes(max(hi - lo for lo, hi in parts)))
             dist = torch.empty(P, dtype=torch.int32, device=self.device)
             for lo, hi in parts:
-                ops.page_edit_distance(d_pool, pool.size, ints[lo:hi], ints[P + lo:P + hi], ints[2 * P + lo:2 * P + hi], ints[3 * P + lo:3 * P + hi], sigma,
-                                       self.scratch, dist=dist[lo:hi])
+                ops.page_edit_distance(d_pool, pool.size, d_ao[lo:hi], d_al[lo:hi], d_bo[lo:hi], d_bl[lo:hi], sigma, scratch, dist=dist[lo:hi])
             out = dist.cpu().numpy()                                          # the one download
         if (out < 0).any():
             raise RuntimeError('omp_page_edit_distance refused a pair (a length above %d, or a range outside the pool)' % LEN_MAX)

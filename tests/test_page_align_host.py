@@ -96,6 +96,34 @@ def test_the_worked_examples():
     assert PA.align_cpu([1, 2], [])[1].tolist() == [0, 0, 2, 0] and PA.align_cpu([], [1, 2])[1].tolist() == [0, 0, 0, 2]
 
 
+def test_table_cpu_and_distance_cpu_share_one_row_recurrence():
+    """table_cpu stacks the rows distance_cpu takes the last of (page_text._rows): the corner is the distance, the table of (b, a) is
+    the transpose, and the table equals the plain triple-min one -- at lengths around one and two 64-character blocks"""
+    rng = np.random.RandomState(5)
+    lengths = (0, 1, 2, 64, 65)
+    for kind in ('sigma 1', 'sigma 26', 'a side of 255'):
+        for la in lengths:
+            for lb in lengths:
+                sigma = 1 if kind == 'sigma 1' else 26
+                a, b = rng.randint(0, sigma, la).astype(np.uint8), rng.randint(0, sigma, lb).astype(np.uint8)
+                if kind == 'a side of 255':
+                    b[:] = PT.NONE
+                D = PA.table_cpu(a, b)
+                assert D.shape == (la + 1, lb + 1) and D.dtype == np.int32 and D.flags['C_CONTIGUOUS'], (kind, la, lb)
+                assert int(D[-1, -1]) == PT.distance_cpu(a, b) == PT.distance_cpu(b, a), (kind, la, lb)
+                assert np.array_equal(PA.table_cpu(b, a), D.T), (kind, la, lb)
+                assert D[0].tolist() == list(range(lb + 1)) and D[:, 0].tolist() == list(range(la + 1))
+                ne = ((a[:, None] != b[None, :]) | (a[:, None] == PT.NONE)).astype(np.int64)
+                want = np.zeros((la + 1, lb + 1), np.int64)
+                want[0], want[:, 0] = np.arange(lb + 1), np.arange(la + 1)
+                for i in range(1, la + 1):
+                    for j in range(1, lb + 1):
+                        want[i, j] = min(want[i - 1, j - 1] + ne[i - 1, j - 1], want[i - 1, j] + 1, want[i, j - 1] + 1)
+                assert np.array_equal(D, want), (kind, la, lb)
+                if kind == 'a side of 255':
+                    assert int(D[-1, -1]) == max(la, lb)
+
+
 def test_pairs_align_cpu_lays_the_maps_out_by_map_off():
     pool = np.concatenate([_codes('abcab'), _codes('abxb'), _codes('b')])
     a_off, a_len, b_off, b_len = [0, 5, 0], [5, 4, 5], [5, 0, 9], [4, 5, 1]
@@ -296,10 +324,16 @@ def test_entry_point_matches_the_header():
     assert res is ctypes.c_int and args == want and len(want) == 16 and 'omp_page_align' in _lib.EXPORTS
     assert 'page_align.hip' in build.SOURCES and 'page_align.hip' not in build.AUDITED
     assert callable(ops.page_align) and callable(ops.page_align_scratch_bytes)
-    src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_align.hip')).read()
+    csrc = os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc')
+    src = open(os.path.join(csrc, 'page_align.hip')).read()
     assert 'extern "C" int omp_page_align(' in src
-    assert 'PA_LEN_MAX = %d' % PT.LEN_MAX in src and 'PA_BLOCK = %d' % PT.BLOCK in src and 'PA_STRIPE = %d' % PT.STRIPE in src
-    assert 'PA_SIGMA_MAX = %d' % PT.SIGMA_MAX in src and 'PA_NONE = %d' % PT.NONE in src
+    # the forward pass and its constants are page_text.hip's: both take them from myers.h, and neither keeps a copy
+    hdr = open(os.path.join(csrc, 'myers.h')).read()
+    assert 'myers.h' in [os.path.basename(h) for h in build.HEADERS] and '#include "myers.h"' in src
+    assert 'PT_LEN_MAX = %d' % PT.LEN_MAX in hdr and 'PT_BLOCK = %d' % PT.BLOCK in hdr and 'PT_STRIPE = %d' % PT.STRIPE in hdr
+    assert 'PT_SIGMA_MAX = %d' % PT.SIGMA_MAX in hdr and 'PT_NONE = %d' % PT.NONE in hdr
+    for unit in (src, open(os.path.join(csrc, 'page_text.hip')).read()):
+        assert not re.search(r'\w*(LEN_MAX|BLOCK|STRIPE|SIGMA_MAX|NONE|CARRY_WORDS)\s*=[^=]', unit)
     assert 'PA_CARRY_BYTES = %d' % ops.PAGE_ALIGN_CARRY_BYTES in src and 'PA_CELL_BYTES = %d' % ops.PAGE_ALIGN_CELL_BYTES in src
     for la, lb in ((64, 65535), (65535, 64), (4097, 4097), (0, 0), (1, 1), (65535, 65535)):
         need = ops.page_align_scratch_bytes(la, lb)

@@ -188,6 +188,37 @@ def test_encode_search_shares_ranges_and_keeps_the_limits():
         PS.encode_search([''], [''.join(chars[i:i + 64]) for i in range(0, 255, 64)])
 
 
+def test_encode_search_gives_the_recorded_pools_and_tables():
+    """encode_search goes through page_text._encode, which encode_pairs shares: the outputs are the ones recorded from encode_search
+    before the two were joined, values, dtypes and shapes"""
+    chars = [chr(0x4e00 + i) for i in range(255)]
+    i32 = lambda *v: np.asarray(v, dtype=np.int32).reshape(-1)               # noqa: E731
+    cases = [
+        # equal strings of one side share a range; a, x, y and z are page characters only
+        ((['ab cd', 'xyz', 'ab cd', ''], ['cd', 'b c', 'cd']),
+         (np.asarray([255, 2, 3, 0, 1, 255, 255, 255, 0, 1, 2, 3, 0], np.uint8), i32(0, 5, 0, 8), i32(5, 3, 5, 0), i32(8, 10, 8), i32(2, 3, 2), 4)),
+        # sigma at its limit, against one empty page
+        (([''], [''.join(chars[:254][i:i + 64]) for i in range(0, 254, 64)]),
+         (np.arange(254).astype(np.uint8), i32(0), i32(0), i32(0, 64, 128, 192), i32(64, 64, 64, 62), 254)),
+        # a page at the length limit, none of its characters in a query
+        ((['z' * PS.LEN_MAX, ''], ['a']),
+         (np.concatenate([np.full(PS.LEN_MAX, 255), [0]]).astype(np.uint8), i32(0, PS.LEN_MAX), i32(PS.LEN_MAX, 0), i32(PS.LEN_MAX), i32(1), 1)),
+        # an empty side: no pages
+        (([], ['ab', 'ab']), (np.asarray([0, 1], np.uint8), i32(), i32(), i32(0, 0), i32(2, 2), 2)),
+    ]
+    for args, want in cases:
+        got = PS.encode_search(*args)
+        assert len(got) == 6 and got[5] == want[5] and type(got[5]) is int, args
+        for g, w in zip(got[:5], want[:5]):
+            assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), (args, g, w)
+    for args, text in ((([''], [''.join(chars[i:i + 64]) for i in range(0, 255, 64)]), 'the queries hold 255 distinct characters; a call takes 254'),
+                       ((['a' * (PS.LEN_MAX + 1)], ['a']), 'a page text holds 65536 characters; the limit is 65535'),
+                       ((['a'], ['']), "query '' holds 0 characters; a query takes 1 .. 64")):
+        with pytest.raises(ValueError) as e:
+            PS.encode_search(*args)
+        assert str(e.value) == text
+
+
 def test_page_index_normalises_per_word():
     recs = [dict(rec='Straße', polys=[]), dict(rec='', polys=[]), dict(lex=None, rec='No', polys=[])]
     text, start, ln = PS.page_index(recs, field='lex')

@@ -100,6 +100,38 @@ def test_encode_pairs_refuses():
             PT.pairs_cpu(**kw)
 
 
+def test_encode_pairs_gives_the_recorded_pools_and_tables():
+    """encode_pairs goes through page_text._encode, which encode_search shares: the outputs are the ones recorded from encode_pairs
+    before the two were joined, values, dtypes and shapes"""
+    many = ''.join(chr(0x100 + k) for k in range(255))
+    i32 = lambda *v: np.asarray(v, dtype=np.int32).reshape(-1)               # noqa: E731
+    cases = [
+        # equal strings of one side share a range; x and q are ground truth only
+        ((['abcab', 'cab', '', 'abcab'], ['abxab', 'abxab', 'q', 'abcab']),
+         (np.asarray([0, 1, 2, 0, 1, 2, 0, 1, 0, 1, 255, 0, 1, 255, 0, 1, 2, 0, 1], np.uint8), i32(0, 5, 8, 0), i32(5, 3, 0, 5), i32(8, 8, 13, 14), i32(5, 5, 1, 5), 3)),
+        # an empty side: no table, so every ground-truth character is 255
+        ((['', ''], ['ab', '']), (np.asarray([255, 255], np.uint8), i32(0, 0), i32(0, 0), i32(0, 2), i32(2, 0), 0)),
+        ((['', 'ba'], ['', 'ab']), (np.asarray([0, 1, 1, 0], np.uint8), i32(0, 0), i32(0, 2), i32(2, 2), i32(0, 2), 2)),
+        (([], []), (np.zeros(0, np.uint8), i32(), i32(), i32(), i32(), 0)),
+        # sigma at its limit: 254 codes, the 255th character is ground truth only
+        (([many[:254]], [many]), (np.concatenate([np.arange(254), np.arange(254), [255]]).astype(np.uint8), i32(0), i32(254), i32(254), i32(255), 254)),
+        # a string at the length limit
+        ((['a' * PT.LEN_MAX], ['']), (np.zeros(PT.LEN_MAX, np.uint8), i32(0), i32(PT.LEN_MAX), i32(PT.LEN_MAX), i32(0), 1)),
+    ]
+    for args, want in cases:
+        got = PT.encode_pairs(*args)
+        assert len(got) == 6 and got[5] == want[5] and type(got[5]) is int, args
+        for g, w in zip(got[:5], want[:5]):
+            assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), (args, g, w)
+    for args, text in ((([many], ['a']), 'the prediction strings hold 255 distinct characters; a call takes 254 -- score such pages on the host with '
+                        'utils.lexicon.edit_distance_cpu'),
+                       ((['a' * (PT.LEN_MAX + 1)], ['a']), 'a page string holds 65536 characters; the limit is 65535'),
+                       ((['a'], ['a' * (PT.LEN_MAX + 1)]), 'a page string holds 65536 characters; the limit is 65535')):
+        with pytest.raises(ValueError) as e:
+            PT.encode_pairs(*args)
+        assert str(e.value) == text
+
+
 # -- page_string ------------------------------------------------------------------------------------------------------------------------
 def test_page_string_strips_then_normalises_and_follows_the_fallbacks():
     recs = [dict(rec='Hel lo', lex=None), dict(rec='W\nx', lex='World'), dict(rec='STRASSE', lex=None)]
@@ -301,11 +333,16 @@ def test_entry_point_matches_the_header():
     assert res is ctypes.c_int and args == want and len(want) == 12 and 'omp_page_edit_distance' in _lib.EXPORTS
     assert 'page_text.hip' in build.SOURCES and 'page_text.hip' not in build.AUDITED
     assert callable(ops.page_edit_distance) and callable(ops.page_scratch_bytes)
-    src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_text.hip')).read()
+    csrc = os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc')
+    src = open(os.path.join(csrc, 'page_text.hip')).read()
     assert 'extern "C" int omp_page_edit_distance(' in src
-    assert 'PT_LEN_MAX = %d' % PT.LEN_MAX in src and 'PT_BLOCK = %d' % PT.BLOCK in src and 'PT_STRIPE = %d' % PT.STRIPE in src
-    assert 'PT_SIGMA_MAX = %d' % PT.SIGMA_MAX in src and 'PT_NONE = %d' % PT.NONE in src
-    assert 'PT_SLICE_BYTES = %d' % ops.PAGE_TEXT_SLICE_BYTES in src and ops.page_scratch_bytes(3) == 3 * ops.PAGE_TEXT_SLICE_BYTES
+    # the constants of the forward pass live in myers.h, which page_align.hip shares, and nowhere else
+    hdr = open(os.path.join(csrc, 'myers.h')).read()
+    assert 'myers.h' in [os.path.basename(h) for h in build.HEADERS] and '#include "myers.h"' in src
+    assert 'PT_LEN_MAX = %d' % PT.LEN_MAX in hdr and 'PT_BLOCK = %d' % PT.BLOCK in hdr and 'PT_STRIPE = %d' % PT.STRIPE in hdr
+    assert 'PT_SIGMA_MAX = %d' % PT.SIGMA_MAX in hdr and 'PT_NONE = %d' % PT.NONE in hdr
+    assert not re.search(r'\w*(LEN_MAX|BLOCK|STRIPE|SIGMA_MAX|NONE|CARRY_WORDS)\s*=[^=]', src)
+    assert 'PT_SLICE_BYTES = %d' % ops.PAGE_TEXT_SLICE_BYTES in hdr and ops.page_scratch_bytes(3) == 3 * ops.PAGE_TEXT_SLICE_BYTES
     assert PT.STRIPE == 64 * PT.BLOCK and PT.LEN_MAX == 65535
     assert PT.chunk_pairs(10, 3 * ops.PAGE_TEXT_SLICE_BYTES + 5) == [(0, 3), (3, 6), (6, 9), (9, 10)] and PT.chunk_pairs(0) == []
     with pytest.raises(ValueError):
