@@ -134,6 +134,9 @@ _SIGS = {
     'omp_debug_rows_tile_choice': (c_int, [c_int, c_int]),
     'omp_debug_cross_q4': (c_int, [c_int]),
     'omp_debug_cross_nt': (c_int, [c_int]),
+    'omp_debug_cross_attn_pairs': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                           c_int, c_void_p]),
     'omp_debug_self_attn_impl': (c_int, [c_int]),
     'omp_debug_fused_self_attn': (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 6 + [c_int, c_int, c_void_p, c_int] + [c_void_p] * 5 +
                                   [c_int, c_void_p]),

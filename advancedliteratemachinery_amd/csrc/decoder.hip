@@ -552,7 +552,8 @@ struct CrossP {
 
 // Slab element types: bf16, float, and bf16s_t = SPLIT-bf16 planes (round 4, the parity engine): every 32-key block of a K / V^T slab is
 // [hi plane | lo plane] of bf16 (the bytes of the fp32 block), value = hi + lo to 16 mantissa bits.  q arrives and the output leaves
-// in fp32; S and PV run as three bf16 matrix-core products each (K_hi q_hi + K_lo q_hi + K_hi q_lo; V_hi p_hi + V_lo p_hi + V_hi p_lo),
+// in fp32 and are split into THREE bf16 planes (exact); S and PV run as five bf16 matrix-core products each (K_hi q_hi + K_lo q_hi + K_hi q_lo +
+// K_lo q_lo + K_hi q_lo2; V_hi p_hi + V_lo p_hi + V_hi p_lo + V_lo p_lo + V_hi p_lo2: what is dropped is 2^-24 relative),
 // so the fp32-grade cross-attention is paced by HBM like the bf16 one instead of by the 16x16x4 fp32 matrix-core rate.  A CPU
 // simulation (tools/sim_cross_planes.py, profiles/r04_sim_cross_planes.txt) shows that NONE of K, V, q, P may stay a single bf16
 // plane under north_star's 1e-3 logit gate.
@@ -603,6 +604,17 @@ constexpr int CROSS_PSTR = 68;   // m, l, pad, pad, o[64]
 __device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) { hi[i] = (bf16_t)v[i]; lo[i] = (bf16_t)(v[i] - (float)hi[i]); }
+}
+// the same with a third plane: x = hi + lo + lo2 exactly (24 mantissa bits).  The cross-attention kernels split q / 8 and P this way: with two
+// planes their 2^-17 relative truncation reached 8e-5 in the output where a few keys compete (scores of standard deviation 2, values 10 apart)
+__device__ __forceinline__ void split8x3(const float* v, bf16x8& hi, bf16x8& lo, bf16x8& lo2) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hi[i] = (bf16_t)v[i];
+    const float r = v[i] - (float)hi[i];
+    lo[i] = (bf16_t)r;
+    lo2[i] = (bf16_t)(r - (float)lo[i]);
+  }
 }
 
 // keys of this group's image and its per-range width.  klen == NULL: M and the launch's kpw, untouched.  Otherwise image b has klen[b]
@@ -690,7 +702,8 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
     if (u < nblk) load_block(kbeg + u * KB, kr[u], vr[u]);
 
   // Q fragments (B operand) of the QT query tiles: query li of the tile (clamped), dims s*KSTEP + g*KPL ..
-  frag qf[QT][PL * CT::DSTEPS];   // split planes: [s] = hi, [DSTEPS + s] = lo of the fp32 query row
+  constexpr int QPL = PL == 2 ? 3 : 1;
+  frag qf[QT][QPL * CT::DSTEPS];   // split planes: [s] = hi, [DSTEPS + s] = lo, [2 DSTEPS + s] = lo2 of the fp32 query row
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
     int qi = t * 16 + li;
@@ -704,7 +717,7 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
         unpack16(ld16<float>(qp + s * 32 + 4), tmp + 4);
 #pragma unroll
         for (int i = 0; i < 8; ++i) tmp[i] *= 0.125f;   // a power of two: commutes with the split
-        split8(tmp, qf[t][s], qf[t][CT::DSTEPS + s]);
+        split8x3(tmp, qf[t][s], qf[t][CT::DSTEPS + s], qf[t][2 * CT::DSTEPS + s]);
       }
     } else {
       const E* qp = reinterpret_cast<const E*>(p.q) + (int64_t)(row0 + qi) * p.ldq + h * DH + g * MM::KPL;
@@ -748,11 +761,13 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
           f32x4 st = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < CT::DSTEPS; ++s) MM::mma(st, kc[sb * CT::DSTEPS + s], qf[t][s]);
-          if constexpr (PL == 2) {   // + K_lo q_hi + K_hi q_lo (K_lo q_lo is 2^-16 relative: dropped)
+          if constexpr (PL == 2) {   // + K_lo q_hi + K_hi q_lo + K_lo q_lo + K_hi q_lo2
 #pragma unroll
             for (int s = 0; s < CT::DSTEPS; ++s) {
               MM::mma(st, kc[NKF + sb * CT::DSTEPS + s], qf[t][s]);
               MM::mma(st, kc[sb * CT::DSTEPS + s], qf[t][CT::DSTEPS + s]);
+              MM::mma(st, kc[NKF + sb * CT::DSTEPS + s], qf[t][CT::DSTEPS + s]);
+              MM::mma(st, kc[sb * CT::DSTEPS + s], qf[t][2 * CT::DSTEPS + s]);
             }
           }
 #pragma unroll
@@ -773,8 +788,8 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
         lpart[t] = lpart[t] * alpha + ps;
         m[t] = mn;
         if constexpr (PL == 2) {
-          frag ph, plo;
-          split8(sc, ph, plo);
+          frag ph, plo, plo2;
+          split8x3(sc, ph, plo, plo2);
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
@@ -782,6 +797,8 @@ __global__ __launch_bounds__(NW * 64) void dec_cross_attn_kernel(CrossP p) {
             MM::mma(ot[t][dt], vc[dt], ph);
             MM::mma(ot[t][dt], vc[4 + dt], ph);
             MM::mma(ot[t][dt], vc[dt], plo);
+            MM::mma(ot[t][dt], vc[4 + dt], plo);
+            MM::mma(ot[t][dt], vc[dt], plo2);
           }
         } else {
           const frag pf = CT::pfrag(sc);
@@ -966,8 +983,9 @@ __global__ __launch_bounds__(256) void dec_cross_attn_q4_kernel(CrossP p) {
     }
   }
 
-  // Q fragments (B operand) of this wave's tile, 1/sqrt(64) folded in (split planes: [st] = hi, [QS + st] = lo of the fp32 row)
-  frag qf[PL * QS];
+  // Q fragments (B operand) of this wave's tile, 1/sqrt(64) folded in (split planes: [st] = hi, [QS + st] = lo, [2 QS + st] = lo2 of the fp32 row)
+  constexpr int QPL = PL == 2 ? 3 : 1;
+  frag qf[QPL * QS];
   {
     int qi = wave * 16 + li;
     if (qi > nrows - 1) qi = nrows - 1;
@@ -980,7 +998,7 @@ __global__ __launch_bounds__(256) void dec_cross_attn_q4_kernel(CrossP p) {
         unpack16(ld16<float>(qp + st * 32 + 4), tmp + 4);
 #pragma unroll
         for (int i = 0; i < 8; ++i) tmp[i] *= 0.125f;
-        split8(tmp, qf[st], qf[QS + st]);
+        split8x3(tmp, qf[st], qf[QS + st], qf[2 * QS + st]);
       }
     } else {
       const E* qp = reinterpret_cast<const E*>(p.q) + (int64_t)(row0 + qi) * p.ldq + h * DH + g * MM::KPL;
@@ -1022,9 +1040,12 @@ __global__ __launch_bounds__(256) void dec_cross_attn_q4_kernel(CrossP p) {
           for (int st = 0; st < QS; ++st) {
             const frag kh = *reinterpret_cast<const frag*>(base + koff[sb][st]);
             MM::mma(sacc, kh, qf[st]);
-            if constexpr (PL == 2) {   // + K_lo q_hi + K_hi q_lo
-              MM::mma(sacc, *reinterpret_cast<const frag*>(base + 4096 + koff[sb][st]), qf[st]);
+            if constexpr (PL == 2) {   // + K_lo q_hi + K_hi q_lo + K_lo q_lo + K_hi q_lo2
+              const frag klo = *reinterpret_cast<const frag*>(base + 4096 + koff[sb][st]);
+              MM::mma(sacc, klo, qf[st]);
               MM::mma(sacc, kh, qf[QS + st]);
+              MM::mma(sacc, klo, qf[QS + st]);
+              MM::mma(sacc, kh, qf[2 * QS + st]);
             }
           }
 #pragma unroll
@@ -1080,14 +1101,17 @@ __global__ __launch_bounds__(256) void dec_cross_attn_q4_kernel(CrossP p) {
       for (int j = 0; j < CH; ++j) {
         const char* base = ring + (sl_c * CH + j) * BLKB;
         if constexpr (PL == 2) {
-          frag ph, plo;
-          split8(sc + j * SPB, ph, plo);
+          frag ph, plo, plo2;
+          split8x3(sc + j * SPB, ph, plo, plo2);
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
             const frag vh = *reinterpret_cast<const frag*>(base + voff[dt]);
+            const frag vlo = *reinterpret_cast<const frag*>(base + 4096 + voff[dt]);
             MM::mma(ot[dt], vh, ph);
-            MM::mma(ot[dt], *reinterpret_cast<const frag*>(base + 4096 + voff[dt]), ph);
+            MM::mma(ot[dt], vlo, ph);
             MM::mma(ot[dt], vh, plo);
+            MM::mma(ot[dt], vlo, plo);
+            MM::mma(ot[dt], vh, plo2);
           }
         } else {
           const frag pf = CT::pfrag(sc + j * SPB);
@@ -1465,7 +1489,7 @@ int launch_cross(CrossP cp, int n_groups, int dtype, int S, int qt, hipStream_t 
   const bool f = dtype == OMP_F32;
   const bool nt_on = cx.cross_nt == 1 || (cx.cross_nt == 2 && n_groups >= 32);
   if (dtype == OMP_BF16X2) {
-    // split-plane slabs (the parity engine): fp32 q / out, three bf16 products per score / value block.  A ring stage is 16 KB;
+    // split-plane slabs (the parity engine): fp32 q / out, five bf16 products per score / value block.  A ring stage is 16 KB;
     // the register-streaming kernel keeps 2 blocks (32 KB) in flight per wave.
     if (q4) {
       // ring geometry, measured at 160 images x 64 rows (profiles/r04h_kbench_cross_split_rings.txt, r04i_*): the more workgroups per CU the
@@ -2135,6 +2159,25 @@ extern "C" int omp_debug_fused_self_attn(const float* x, const float* ln_g, cons
   fp.seq = seq; fp.seq_ld = seq_ld; fp.word = word_emb; fp.pos_tab = pos_tab; fp.emb_g = emb_g; fp.emb_b = emb_b;
   fp.x_out = x_out;
   return launch_fused_sa(fp, embed != 0, (hipStream_t)s);
+}
+
+// omp_dec_cross_attn_step with split-pair output rows (CrossP.lo_off > 0): what step_launch_x3 launches over split-plane slabs, on its own
+extern "C" int omp_debug_cross_attn_pairs(const void* q, int64_t ldq, const void* K, const void* Vt, int64_t img_stride,
+                                          int Mpad, const uint8_t* key_mask, const int32_t* key_len, const int32_t* groups,
+                                          int n_groups, int q_tiles, int R, float* partial, void* out, int64_t ldo, int lo_off,
+                                          int dtype, int M, int nH, int n_split, omp_stream_t s) {
+  OMP_CHECK_ARG(q && K && Vt && groups && out, "omp_debug_cross_attn_pairs: null pointer");
+  OMP_CHECK_ARG(R > 0, "omp_debug_cross_attn_pairs: bad R");
+  OMP_CHECK_ARG(dtype == OMP_BF16X2, "omp_debug_cross_attn_pairs: split-plane slabs only (dtype OMP_BF16X2)");
+  OMP_CHECK_ARG(n_groups > 0 && n_split > 0 && M > 0, "omp_debug_cross_attn_pairs: bad sizes");
+  OMP_CHECK_ARG(ldq % 4 == 0 && ((uintptr_t)q % 16) == 0, "omp_debug_cross_attn_pairs: split-plane slabs take 16-byte aligned fp32 q rows");
+  // the ring kernel stores four bf16 of the hi and of the lo plane at a time
+  OMP_CHECK_ARG(lo_off > 0 && lo_off % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)out % 8) == 0,
+                "omp_debug_cross_attn_pairs: pair rows take lo_off > 0, lo_off and ldo multiples of 4 bf16 elements and an 8-byte aligned out");
+  CrossP cp;
+  cp.q = q; cp.ldq = ldq; cp.K = K; cp.V = Vt; cp.img_stride = img_stride; cp.kmask = key_mask; cp.klen = key_len; cp.groups = groups;
+  cp.out = out; cp.ldo = ldo; cp.partial = partial; cp.M = M; cp.Mpad = Mpad; cp.nH = nH; cp.R = R; cp.kpw = 0; cp.lo_off = lo_off;
+  return launch_cross(cp, n_groups, dtype, n_split, q_tiles, (hipStream_t)s);
 }
 
 extern "C" int omp_debug_cross_nt(int on) {

@@ -71,6 +71,13 @@ int omp_debug_rows_tile_choice(int R, int mid); /* host logic, no launch: rows p
 int omp_debug_rows_tile(int rtt);        /* decoder row-owner chains (bf16): rows per workgroup = 16 x rtt, 0 = chosen by row count (default), 2..5 forced */
 int omp_debug_cross_nt(int on);          /* non-temporal K / V^T loads in the cross-attention kernels: 1 = always (default), 2 = only from 32 groups per launch, 0 = never */
 int omp_debug_cross_q4(int on);          /* 1 = LDS-ring cross-attention for 33..64 rows/image in 64-key chunks, non-temporal DMA (default), 2 = one 32-key block per step, 4 = chunks with temporal loads, 0 = register-streaming kernel */
+/* omp_dec_cross_attn_step (include/omp355.h) with SPLIT-PAIR output rows, as the bf16x3 engine launches it over split-plane slabs: dtype must
+ * be OMP_BF16X2; row r of `out` (bf16, ldo elements apart) holds hi = bf16(value) in columns [0, 64 nH) and lo = bf16(value - hi) lo_off
+ * columns further.  OMP_ERR_INVALID besides the step's own refusals: another dtype, lo_off <= 0, lo_off or ldo no multiple of 4, `out` not
+ * 8-byte aligned (the ring kernel stores four bf16 at a time) */
+int omp_debug_cross_attn_pairs(const void* q, int64_t ldq, const void* K, const void* Vt, int64_t img_stride, int Mpad,
+                               const uint8_t* key_mask, const int32_t* key_len, const int32_t* groups, int n_groups, int q_tiles, int R,
+                               float* partial, void* out, int64_t ldo, int lo_off, int dtype, int M, int nH, int n_split, omp_stream_t s);
 
 /* Single teacher-forced step that also leaves logits in plan->logits (parity tests). */
 int omp_decoder_step_logits(const omp_decoder_plan* plan, int pos, omp_stream_t s);

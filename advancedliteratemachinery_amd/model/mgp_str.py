@@ -236,7 +236,7 @@ class MGPSTR(nn.Module):
 
     def _encode_x3(self, img, e, B, T):
         """The parity engine's encoder: fp32 residual stream, split-pair GEMM operands, split-plane K / V^T slabs, the 257-token
-        attention on the blocked cross-attention kernels (three bf16 products per score / value block)."""
+        attention on the blocked cross-attention kernels (five bf16 products per score / value block)."""
         c = self.cfg
         E, nH, S = c['embed'], c['heads'], ops.SPLIT
         f32 = torch.float32

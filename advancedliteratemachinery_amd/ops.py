@@ -338,6 +338,20 @@ def dec_cross_attn_step(q, K, Vt, img_stride, Mpad, key_mask, groups, n_groups, 
     _lib.check(rc, 'omp_dec_cross_attn_step')
 
 
+def cross_attn_pairs(q, K, Vt, img_stride, Mpad, key_mask, groups, n_groups, q_tiles, partial, out, lo_off, M, nH, n_split, key_len=None):
+    """debug/testing: dec_cross_attn_step over SPLIT-PLANE slabs (fp32 q, bf16 K / V^T planes) whose output rows are split-bf16 pairs, as
+    the bf16x3 engine launches it: out [R, >= lo_off + 64 nH] bf16, hi = bf16(value) in columns [0, 64 nH), lo = bf16(value - hi) lo_off
+    columns further (omp_debug_cross_attn_pairs)."""
+    if q.dtype != torch.float32 or K.dtype != torch.bfloat16 or Vt.dtype != torch.bfloat16 or out.dtype != torch.bfloat16:
+        raise TypeError('cross_attn_pairs: fp32 q, bf16 K and V^T planes, bf16 pair rows')
+    if key_len is not None and (key_len.dtype != torch.int32 or not key_len.is_contiguous()):
+        raise TypeError('cross_attn_pairs: key_len is a contiguous int32 device tensor')
+    rc = _lib.lib().omp_debug_cross_attn_pairs(ptr(q), q.stride(0), ptr(K), ptr(Vt), img_stride, Mpad, ptr(key_mask), ptr(key_len),
+                                               ptr(groups), n_groups, q_tiles, q.shape[0], ptr(partial), ptr(out), out.stride(0),
+                                               int(lo_off), OMP_BF16X2, M, nH, n_split, stream())
+    _lib.check(rc, 'omp_debug_cross_attn_pairs')
+
+
 def head_sample(logits, cfg, seq, probs, finished, lengths, d_pos, advance=True):
     R = logits.shape[0]
     rc = _lib.lib().omp_head_softmax_mask_argmax(ptr(logits), logits.stride(0), R, ctypes.byref(cfg), ptr(seq),
