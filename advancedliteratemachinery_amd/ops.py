@@ -72,8 +72,10 @@ def layernorm_sampled(x, gamma, beta, B, H, W, step, group, out_dtype=None, eps=
 
 def gemm(A, W, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None, M=None, lda=None,
          ldw=None, ldc=None, N=None, K=None, bias_row=None, bias_row_stride=0, trans_rows=0, trans_ld=0,
-         ln=None, ln_eps=1e-5, small_m=False, store_mode=0, kv=None, bias_along_m=False, out_noresidual=None, a_wrap=0):
+         ln=None, ln_eps=1e-5, small_m=False, store_mode=0, kv=None, bias_along_m=False, out_noresidual=None, a_wrap=0,
+         bias_row_mod=0, bias_row_off=0):
     """out[M,N] = act(A[M,K] @ W[N,K]^T + bias) + residual.  A/W may be strided row views (lda/ldw).
+    bias_row_mod > 0: bias is a table of bias_row_stride-pitched rows and row m takes table row (bias_row_off + m) % bias_row_mod.
     out_noresidual (optional, with a residual): also receives act(A W^T + bias) without the residual.
     a_wrap > 0: bf16x3 product -- A is a split-bf16 pair tensor [M, a_wrap] = [hi | lo], W the [N, K] = [hi | hi | lo] image of an
     fp32 weight (split_weight3), K = 3/2 a_wrap.  out_dtype=SPLIT: the result is written as split pairs [M, 2N]."""
@@ -92,6 +94,7 @@ def gemm(A, W, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None,
     a = _lib.GemmArgs()
     a.A, a.lda, a.W, a.ldw = ptr(A), lda, ptr(W), ldw
     a.bias, a.bias_row, a.bias_row_stride = ptr(bias), ptr(bias_row), bias_row_stride
+    a.bias_row_mod, a.bias_row_off = int(bias_row_mod), int(bias_row_off)
     a.residual, a.ldr = ptr(residual), (residual.stride(-2) if residual is not None else 0)
     a.C, a.ldc = ptr(out), ldc
     a.M, a.N, a.K = M, N, K
@@ -618,14 +621,15 @@ def kv_project_rows(rows, wstream, wave_stride, bias, out, B, M, Mpad, n_slabs, 
     return out
 
 
-def dec_rows_mid(att, x, wstream, wave_stride, out_b, ln_g, ln_b, qbias_tab, d_pos, q=None, eps=1e-5, x3=False, xcd_mask=0):
+def dec_rows_mid(att, x, wstream, wave_stride, out_b, ln_g, ln_b, qbias_tab, d_pos, q=None, eps=1e-5, x3=False, xcd_mask=0, pos_mod=0):
     """x += att Wo^T + bo;  q = bf16(LayerNorm(x) Wq^T + qbias_tab[*d_pos])  -- one launch, a workgroup owns 80 rows (include/omp355.h).
+    pos_mod > 0 (bf16 chains): row r takes qbias_tab[r % pos_mod] and d_pos is not read.
     x3: the parity engine's chain -- att as split pairs bf16 [R, 1024], q fp32, split weight stream, 48 rows per workgroup."""
     R = x.shape[0]
     if q is None:
         q = torch.empty((R, 512), dtype=torch.float32 if x3 else torch.bfloat16, device=x.device)
     a = _lib.DecRowsArgs()
-    a.x3, a.xcd_mask = 1 if x3 else 0, int(xcd_mask)
+    a.x3, a.xcd_mask, a.pos_mod = 1 if x3 else 0, int(xcd_mask), int(pos_mod)
     a.R, a.eps, a.d_pos, a.x, a.att = R, float(eps), ptr(d_pos), ptr(_c(x, 'x')), ptr(_c(att, 'att'))
     a.wstream, a.wave_stride = ptr(wstream), int(wave_stride)
     a.out_b, a.ln_g, a.ln_b, a.qbias_tab, a.q = ptr(out_b), ptr(ln_g), ptr(ln_b), ptr(qbias_tab), ptr(q)

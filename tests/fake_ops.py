@@ -22,9 +22,11 @@ def _slot(kl):
 
 
 def gemm(A, W, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None, M=None, N=None, K=None,
-         store_mode=0, kv=None, bias_along_m=False, **_):
+         store_mode=0, kv=None, bias_along_m=False, bias_row_mod=0, bias_row_off=0, **_):
     y = A.float() @ W.float().t()
-    if bias is not None:
+    if bias is not None and bias_row_mod > 0:       # the table's per-row form: row m takes table row (bias_row_off + m) % bias_row_mod
+        y = y + bias[(bias_row_off + torch.arange(y.shape[0])) % bias_row_mod][:, :y.shape[1]]
+    elif bias is not None:
         y = y + (bias[:, None] if bias_along_m else bias)
     y = F.gelu(y) if act == ACT_GELU else (F.relu(y) if act == ACT_RELU else y)
     if store_mode == STORE_KBLK:

@@ -9,7 +9,9 @@ Every launch goes through run_case:
     every row of A from M to 63); the output must be finite (gate 0) and equal the float64 restatement;
   * pitch classes: 'vec' (ldc and ldr multiples of the 16-byte chunk), 'scalar' (ldc not a multiple of 4 elements: store4 element by
     element), 'ldr_odd' (ldc even, ldr odd);
-  * out is residual (in place) must equal out of place bit for bit.
+  * out is residual (in place) must equal out of place bit for bit;
+  * bias 'table' (bias_row_mod / bias_row_off: row m takes table row (off + m) % mod): the device table has exactly mod rows between NaN
+    guard rows, and next to float64 every row must equal, bit for bit, its row of the one-row launch (bias_row = [j]) of its table row.
 Stray accesses are detected BY VALUE only: nothing here looks at a kernel's code or provokes a fault.
 
 ref_gemm / ref_ln_gemm are the float64 restatements (tests/test_gemm_reference.py pins them to plain torch and to tests/fake_ops.gemm, and
@@ -118,14 +120,19 @@ def krec(kind, name, err, tol, note='', report=False):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # float64 restatements
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def ref_gemm(A, W, bias=None, bias_mode='n', act=ACT_NONE, residual=None, out='fp64', row=0):
+def ref_gemm(A, W, bias=None, bias_mode='n', act=ACT_NONE, residual=None, out='fp64', row=0, mod=0, off=0):
     """act(A W^T + bias) + residual in float64 on the operands as the kernel sees them (already rounded to the operand type).
-    bias_mode: 'n' bias[n], 'm' bias[m], 'row' bias[row][n] of a table.  GELU is the erf form.  out: 'fp64' unrounded (fp32 destinations
-    are compared with it), 'bf16' rounded once to bf16, 'split' -> (hi plane, lo plane) of the split-bf16 pair rows."""
+    bias_mode: 'n' bias[n], 'm' bias[m], 'row' bias[row][n] of a table, 'table' the table's per-row form: row m takes
+    bias[(off + m) % mod][n].  GELU is the erf form.  out: 'fp64' unrounded (fp32 destinations are compared with it), 'bf16' rounded
+    once to bf16, 'split' -> (hi plane, lo plane) of the split-bf16 pair rows."""
     y = A.double() @ W.double().t()
     if bias is not None:
         b = bias.double()
-        y = y + (b[:, None] if bias_mode == 'm' else b[row] if bias_mode == 'row' else b)
+        if bias_mode == 'table':
+            for m in range(y.shape[0]):
+                y[m] += b[(off + m) % mod]
+        else:
+            y = y + (b[:, None] if bias_mode == 'm' else b[row] if bias_mode == 'row' else b)
     y = gelu64(y) if act == ACT_GELU else (y.clamp_min(0.0) if act == ACT_RELU else y)
     if residual is not None:
         y = y + residual.double()
@@ -154,13 +161,16 @@ def wrap_a(A, K, a_wrap):
 # cases
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def case(sel, dtn, out, M, N, K, bias='n', act=ACT_NONE, res=False, inplace=False, c2=False, trans=0, a_wrap=0, pitch='vec', ln=None,
-         rows=None, seed=1, plant=False, tail=VIEW_LEAD):
-    """sel: selector; dtn: operand type; out: 'bf16' / 'fp32' / 'split'; bias: None / 'n' / 'm' / 'row'; res: residual of the destination's
-    type; inplace: out is residual; c2: second destination; trans: trans_rows (> 0: M = 3 * trans, transposed store with trans_ld >
-    trans_rows); a_wrap: A is [M, a_wrap] pair rows; ln: eps of the fused LayerNorm (A is the fp32 stream); rows: rows of the host
-    operands (>= M; the launch takes the first M -- rows are independent); plant: LayerNorm edge rows; tail: NaN rows behind A"""
+         rows=None, seed=1, plant=False, tail=VIEW_LEAD, mod=0, off=0, one=None, hint=False):
+    """sel: selector; dtn: operand type; out: 'bf16' / 'fp32' / 'split'; bias: None / 'n' / 'm' / 'row' / 'table'; res: residual of the
+    destination's type; inplace: out is residual; c2: second destination; trans: trans_rows (> 0: M = 3 * trans, transposed store with
+    trans_ld > trans_rows); a_wrap: A is [M, a_wrap] pair rows; ln: eps of the fused LayerNorm (A is the fp32 stream); rows: rows of
+    the host operands (>= M; the launch takes the first M -- rows are independent); plant: LayerNorm edge rows; tail: NaN rows behind A.
+    bias 'table': a device table of exactly `mod` rows between NaN guard rows; row m takes row (off + m) % mod (bias_row_mod /
+    bias_row_off), or, one = j, every row takes row j through bias_row = [j] (the one-row form on the same table); hint: the split-K
+    hint (small_m_splitk)"""
     return dict(sel=sel, dtn=dtn, out=out, M=M, N=N, K=K, bias=bias, act=act, res=res or inplace, inplace=inplace, c2=c2, trans=trans,
-                a_wrap=a_wrap, pitch=pitch, ln=ln, rows=rows or M, seed=seed, plant=plant, tail=tail)
+                a_wrap=a_wrap, pitch=pitch, ln=ln, rows=rows or M, seed=seed, plant=plant, tail=tail, mod=mod, off=off, one=one, hint=hint)
 
 
 def tol_key(c):
@@ -171,6 +181,8 @@ def tol_key(c):
 def tag(c):
     t = 'gemm[k%d,%s->%s,%dx%dx%d' % (c['sel'], c['dtn'], c['out'], c['M'], c['N'], c['K'])
     t += ',bias %s' % c['bias'] if c['bias'] else ',no bias'
+    if c['bias'] == 'table':
+        t += ' of %d rows, ' % c['mod'] + ('(%d + m) %% %d' % (c['off'], c['mod']) if c['one'] is None else 'row %d' % c['one'])
     if c['act']:
         t += ',' + ACT_NAMES[c['act']]
     for k, s in (('inplace', 'in place'), ('c2', 'C2'), ('trans', 'trans_out'), ('a_wrap', 'a_wrap'), ('plant', 'planted rows')):
@@ -192,13 +204,16 @@ def ln_plant_rows(M):
     return (0 if M >= 2 else None, M - 1 if M >= 3 else None)
 
 
+PTABLE_ROWS = 7   # rows of the host table the per-row bias cases cut theirs from (the first `mod`)
+
+
 @functools.lru_cache(maxsize=6)
 def host(dtn, rows, N, K, a_wrap, seed, ln):
     """CPU operands, rounded to the types the kernel reads them in"""
     dt = DT[dtn]
     ka = a_wrap or K
     h = dict(W=(rnd(N, K, seed=seed + 1) / math.sqrt(K)).to(dt), bias_n=rnd(N, seed=seed + 2), bias_m=rnd(rows, seed=seed + 3),
-             table=rnd(5, N, seed=seed + 4), res_bf16=rnd(rows, N, seed=seed + 5).to(torch.bfloat16), res_fp32=rnd(rows, N, seed=seed + 6))
+             table=rnd(5, N, seed=seed + 4), ptable=rnd(PTABLE_ROWS, N, seed=seed + 9), res_bf16=rnd(rows, N, seed=seed + 5).to(torch.bfloat16), res_fp32=rnd(rows, N, seed=seed + 6))
     if ln:
         h['A'] = rnd(rows, K, seed=seed) * 1.5 + 0.2
         h['g'], h['b'] = rnd(K, seed=seed + 7) * 0.1 + 1, rnd(K, seed=seed + 8) * 0.1
@@ -242,9 +257,11 @@ def reference(c, h, A):
     """float64 (out, out2, raw, raw2) of case c on host operands h with the A rows `A` ([M, ...]): out / out2 as the destination holds
     them (rounded once to bf16; a (hi, lo) pair for split rows), raw / raw2 the unrounded values the absolute gates are taken against"""
     M = c['M']
-    bias = {None: None, 'n': h['bias_n'], 'm': h['bias_m'][:M], 'row': h['table']}[c['bias']]
+    bias = {None: None, 'n': h['bias_n'], 'm': h['bias_m'][:M], 'row': h['table'], 'table': h['ptable'][:c['mod']]}[c['bias']]
     res = h['res_' + ('bf16' if c['out'] == 'bf16' else 'fp32')][:M] if c['res'] else None
-    kw = dict(bias=bias, bias_mode=c['bias'] or 'n', act=c['act'], row=3)
+    kw = dict(bias=bias, bias_mode=c['bias'] or 'n', act=c['act'], row=3, mod=c['mod'], off=c['off'])
+    if c['bias'] == 'table' and c['one'] is not None:
+        kw.update(bias_mode='row', row=c['one'])
     if c['ln'] is not None:
         f = lambda **k: ref_ln_gemm(A, h['g'], h['b'], c['ln'], h['W'], DT[c['dtn']], **k)
     else:
@@ -259,21 +276,23 @@ def reference(c, h, A):
 def gpu_launch(call):
     """omp_gemm_bias_act on the views of `call`, its selector forced (and 0 restored)"""
     from advancedliteratemachinery_amd import ops
-    ops.force_gemm_kernel(call['sel'])
+    ops.force_gemm_kernel(0 if call['hint'] else call['sel'])   # under the split-K hint the library's own rule must answer 4 (the prefill's path)
     try:
         ops.gemm(call['A'], call['W'], call['bias'], residual=call['residual'], act=call['act'], out=call['out'],
                  out_dtype=ops.SPLIT if call['split'] else None, M=call['M'], N=call['N'], K=call['K'], ldc=call['ldc'],
                  bias_row=call['bias_row'], bias_row_stride=call['bias_row_stride'], trans_rows=call['trans_rows'], trans_ld=call['trans_ld'],
-                 ln=call['ln'], ln_eps=call['ln_eps'], bias_along_m=call['bias_mode'] == 'm', out_noresidual=call['out2'], a_wrap=call['a_wrap'])
+                 ln=call['ln'], ln_eps=call['ln_eps'], bias_along_m=call['bias_mode'] == 'm', out_noresidual=call['out2'], a_wrap=call['a_wrap'],
+                 bias_row_mod=call['bias_row_mod'], bias_row_off=call['bias_row_off'], small_m=call['hint'], store_mode=call.get('store_mode', 0),
+                 kv=call.get('kv'))
     finally:
         ops.force_gemm_kernel(0)
     torch.cuda.synchronize()
 
 
-def run_case(c, launch=gpu_launch, device=DEV, A=None, report=True, expect=None):
+def run_case(c, launch=gpu_launch, device=DEV, A=None, report=True, expect=None, expect_msg=None):
     """Build the guarded views of case c, launch, check -> (records, outputs {name: clone of the destination view}).
     A: host A rows [M, ...] instead of the case's own (planted inputs).  expect: an OMP_ERR_* code the call must be refused with (nothing
-    runs: every destination keeps its sentinels)."""
+    runs: every destination keeps its sentinels); expect_msg: a text the refusal's message (behind the code) must hold."""
     out = []
     M, N, K, dt = c['M'], c['N'], c['K'], DT[c['dtn']]
     h = host(c['dtn'], c['rows'], N, K, c['a_wrap'], c['seed'], c['ln'] is not None)
@@ -303,10 +322,16 @@ def run_case(c, launch=gpu_launch, device=DEV, A=None, report=True, expect=None)
     C2b = C2v = None
     if c['c2']:
         C2b, C2v = guarded_view(M, N, ldc + 16, odt, sent_bits(odt), None, device)
-    bias = {None: None, 'n': h['bias_n'], 'm': h['bias_m'][:M].contiguous(), 'row': h['table']}[c['bias']]
+    bias = {None: None, 'n': h['bias_n'], 'm': h['bias_m'][:M].contiguous(), 'row': h['table'], 'table': h['ptable'][:c['mod']]}[c['bias']]
+    bias_row, bias_ld, per_row = (3 if c['bias'] == 'row' else None), (N if c['bias'] == 'row' else 0), False
+    if c['bias'] == 'table':   # exactly mod rows between NaN rows, at a pitch of its own: a read of any other row shows up by value
+        bias_ld = _pitch_in(N, 4)
+        _, bias = guarded_view(c['mod'], N, bias_ld, torch.float32, nan_bits(torch.float32), bias.to(device), device)
+        bias_row, per_row = c['one'], c['one'] is None
     call = dict(sel=c['sel'], A=Av, W=Wv, bias=None if bias is None else bias.to(device), bias_mode=c['bias'],
-                bias_row=torch.tensor([3], dtype=torch.int32, device=device) if c['bias'] == 'row' else None,
-                bias_row_stride=N if c['bias'] == 'row' else 0, residual=Rv, act=c['act'], out=Cv, out2=C2v, split=c['out'] == 'split',
+                bias_row=torch.tensor([bias_row], dtype=torch.int32, device=device) if bias_row is not None else None,
+                bias_row_stride=bias_ld, bias_row_mod=c['mod'] if per_row else 0, bias_row_off=c['off'] if per_row else 0, hint=c['hint'],
+                residual=Rv, act=c['act'], out=Cv, out2=C2v, split=c['out'] == 'split',
                 M=M, N=N, K=K, ldc=ldc, trans_rows=c['trans'], trans_ld=ldc if c['trans'] else 0, a_wrap=c['a_wrap'],
                 ln=None if c['ln'] is None else (h['g'].to(device), h['b'].to(device)), ln_eps=c['ln'] if c['ln'] is not None else 1e-5)
     err = ''
@@ -315,7 +340,7 @@ def run_case(c, launch=gpu_launch, device=DEV, A=None, report=True, expect=None)
     except RuntimeError as e:
         err = str(e)
     if expect is not None:
-        why = '' if '(%d)' % expect in err else (err or 'no error')
+        why = '' if '(%d)' % expect in err and (expect_msg or '') in err.partition('): ')[2] else (err or 'no error')
         out.append(krec('refusal', name + ': refused with %d%s' % (expect, '' if not why else ' -- ' + why), 0 if not why else 1, 0))
     elif err:
         out.append(krec('launch', name + ': ' + err, 1, 0))
@@ -656,4 +681,174 @@ def ln_constant_row(dtn, M, N, K, o1, launch=gpu_launch, device=DEV):
     if o2:
         rc = ln_plant_rows(M)[0]
         same_bits(out, tag(dict(c, ln=1e-5, plant=True)) + ': constant row == the product of the rounded beta, bit for bit', o1[rc], o2['C'][rc])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the bias table's per-row form (bias_row_mod / bias_row_off: the batched prompt prefill's products)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+TABLE_MODS = (1, 2, 6, 7)
+
+
+def table_offs(mod):
+    """0, a small offset and one beyond the table (mod + 3: no multiple of mod at mod 2, 6, 7)"""
+    return (0, 4, mod + 3)
+
+
+def one_row_outputs(c, launch=gpu_launch, device=DEV, rows=None):
+    """the one-row form of table case c (bias_row = [j], the same forced selector, the same operands) for every j in `rows` (all of the
+    table) -> (records, {j: outputs}).  Each launch is held to float64 like any other case."""
+    recs, ones = [], {}
+    for j in (range(c['mod']) if rows is None else rows):
+        r, o = run_case(dict(c, one=j, off=0), launch, device, report=False)
+        recs += r
+        ones[j] = o
+    return recs, ones
+
+
+def table_bits(out, c, outs, ones):
+    """the property the prefill pass rests on: row m of the per-row launch == row m of the one-row launch of table row (off + m) % mod,
+    bit for bit, in every destination"""
+    M = c['M']
+    idx = (c['off'] + torch.arange(M)) % c['mod']
+    for k in outs:
+        if any(k not in ones.get(j, {}) for j in set(idx.tolist())):
+            out.append(krec('bits', tag(c) + ': %s: a one-row launch is missing' % k, 1, 0))
+            continue
+        want = torch.stack([ones[int(j)][k][m] for m, j in enumerate(idx.tolist())])
+        same_bits(out, tag(c) + ': %s row m == the one-row form of table row (off + m) %% mod, bit for bit' % k, outs[k], want)
+
+
+def run_table(c, launch=gpu_launch, device=DEV, ones=None):
+    """both gates of a per-row table case: float64 (run_case) and bit equality with the one-row form -> records"""
+    recs, outs = run_case(c, launch, device, report=False)
+    if ones is None:
+        r1, ones = one_row_outputs(c, launch, device, rows=sorted({(c['off'] + m) % c['mod'] for m in range(c['M'])}))
+        recs += r1
+    if outs:
+        table_bits(recs, c, outs, ones)
+    return recs
+
+
+SMALL_TYPES = (('bf16', 'bf16'), ('bf16', 'fp32'), ('fp32', 'fp32'))
+LN_TIE_MARGIN = 16 * 2.0 ** -24   # of max(1, |y|): the mean of K terms, the variance, its inverse root, the scale and the shift each round in fp32
+
+
+def ln_resolvable(X, g, b, eps, W, margin=LN_TIE_MARGIN, share=0.1):
+    """False when an element of the float64-normalised rows lies within `margin` * max(1, |y|) of the midpoint of two neighbouring bf16
+    values AND rounding it the other way could move an output of its row by more than `share` of the tightest gate of a bf16 LayerNorm
+    case (one bf16 step of the element times the largest |w| of its column of W^T, against the row's max |y W^T|).
+    ref_ln_gemm rounds the normalised row to bf16 where the prologue does; that close to a tie no fp32 LayerNorm can tell which way the
+    float64 value rounds, the operand element moves by a whole bf16 step and the row's float64 reference is the reference of another
+    operand -- 6e-4 of the row's max at 64 x 16 x 128 on an MI355X, where one element of 8192 (-1.5117188) sat 3e-8 (relative) from a tie.
+    Decided from the float64 values and the formats alone, never from a kernel's output."""
+    y = F.layer_norm(X.double(), (X.shape[-1],), g.double(), b.double(), eps)
+    yb = y.to(torch.bfloat16)
+    bits = yb.view(torch.int16).to(torch.int32)
+    dist, step = torch.full_like(y, float('inf')), torch.zeros_like(y)
+    for d in (1, -1):
+        nb = (bits + d).clamp(-32768, 32767).to(torch.int16).view(torch.bfloat16).double()
+        mid = (yb.double() + nb) / 2
+        ok = torch.isfinite(mid)
+        dist = torch.minimum(dist, torch.where(ok, (y - mid).abs(), torch.full_like(y, float('inf'))))
+        step = torch.maximum(step, torch.where(ok, (yb.double() - nb).abs(), torch.zeros_like(y)))
+    effect = step * W.double().abs().amax(0)[None, :] / (yb.double() @ W.double().t()).abs().amax(1, keepdim=True).clamp_min(1e-30)
+    gate = min(v[0] for k, v in TOL.items() if k[0] == 'ln' and k[1] == 'bf16')
+    return not bool(((dist <= margin * y.abs().clamp_min(1.0)) & (effect > share * gate)).any().item())
+
+
+def ln_seed(dtn, N, K, eps, first):
+    """the first seed of first, first + 1000, ... whose 64 LayerNorm input rows are resolvable (bf16 operands; fp32 operands are not rounded)"""
+    if dtn != 'bf16':
+        return first
+    for seed in range(first, first + 1000 * 500, 1000):
+        h = host(dtn, 64, N, K, 0, seed, True)
+        if ln_resolvable(h['A'], h['g'], h['b'], eps, h['W']):
+            return seed
+    raise AssertionError('no resolvable LayerNorm input among 500 seeds')
+
+
+def check_table_small(dtn, out, ln):
+    """selector 4 under the split-K hint: M at every MF boundary (below 16 MF the lanes of rows beyond M form a table index too), N in
+    (16, 20, 512), one K tile group, every (mod, off).  The one-row launches are shared by the twelve (mod, off) of a shape: every
+    table is the first `mod` rows of one host table, and a row's bits cannot depend on how many rows lie behind it.  Behind the LayerNorm
+    prologue the bf16 operand rows are drawn from the first seed whose normalised rows stay clear of a bf16 rounding tie (ln_resolvable)."""
+    recs = []
+    K = 128 if dtn == 'bf16' else 64
+    for N in (16, 20, 512):
+        seed = ln_seed(dtn, N, K, 1e-5, N) if ln else N
+        for M in EDGE_M:
+            base = case(4, dtn, out, M, N, K, bias='table', mod=PTABLE_ROWS, ln=1e-5 if ln else None, rows=64, seed=seed, tail=64, hint=True,
+                        pitch='scalar' if N == 20 else 'vec')
+            r1, ones = one_row_outputs(base)
+            recs += r1
+            for mod in TABLE_MODS:
+                for off in table_offs(mod):
+                    recs += run_table(dict(base, mod=mod, off=off), ones=ones)
+    return fold(recs, 'gemm[k4,%s->%s%s] per-row bias table' % (dtn, out, ',LN' if ln else ''))
+
+
+def table_epilogues(sel, M, N, K, pitch):
+    """the epilogues a per-row table goes with, as accepts() filters them: plain / ReLU / GELU into bf16 and fp32, split pairs, the
+    fp32 residual in place (the pass's own form), residual + C2"""
+    kw = dict(bias='table', pitch=pitch)
+    cs = [case(sel, 'bf16', 'bf16', M, N, K, **kw),
+          case(sel, 'bf16', 'bf16', M, N, K, act=ACT_RELU, **kw),
+          case(sel, 'bf16', 'bf16', M, N, K, act=ACT_GELU, **kw),
+          case(sel, 'bf16', 'fp32', M, N, K, inplace=True, **kw),
+          case(sel, 'bf16', 'fp32', M, N, K, act=ACT_GELU, **kw),
+          case(sel, 'bf16', 'fp32', M, N, K, act=ACT_RELU, res=True, **kw),
+          case(sel, 'bf16', 'fp32', M, N, K, res=True, c2=True, **kw),
+          case(sel, 'bf16', 'bf16', M, N, K, res=True, c2=True, **kw),
+          case(sel, 'bf16', 'split', M, N, K, **kw),
+          case(sel, 'bf16', 'split', M, N, K, act=ACT_GELU, **kw)]
+    return [c for c in cs if accepts(c)]
+
+
+TABLE_TILE_SHAPES = {6: ((65, 127, 129), (64, 72, 67)), 5: ((129, 257), (128, 136, 131))}
+TABLE_TILE_MODS = ((6, 4), (7, 10), (2, 5), (1, 4))   # (mod, off), taken in turn: off is no multiple of mod but at mod 1, M >= 2 mod + 1
+
+
+def check_table_tile(sel, N):
+    """selectors 5 / 6 at ragged M, N = tile, tile + 8 and tile + 3 (the 4-value path at the edge), vector and scalar pitches, every
+    epilogue of table_epilogues; fp32 operands once per pitch"""
+    recs, i = [], 0
+    for M in TABLE_TILE_SHAPES[sel][0]:
+        for pitch in ('vec', 'scalar'):
+            cs = table_epilogues(sel, M, N, 128, pitch)
+            if M == TABLE_TILE_SHAPES[sel][0][0]:
+                cs.append(case(sel, 'fp32', 'fp32', M, N, 64, bias='table', res=True, pitch=pitch))
+            for c in cs:
+                mod, off = TABLE_TILE_MODS[i % len(TABLE_TILE_MODS)]
+                i += 1
+                recs += run_table(dict(c, mod=mod, off=off))
+    return fold(recs, 'gemm[k%d,N=%d] per-row bias table' % (sel, N))
+
+
+def check_table_ring4():
+    """the 4-stage ring of the 64x64 kernel (more than 512 tiles) with a per-row table: one 1025 x 2048 product of one K tile pair"""
+    return fold(run_table(case(6, 'bf16', 'bf16', 1025, 2048, 128, bias='table', mod=7, off=10)), 'gemm[k6] per-row bias table, 4-stage ring, 1025x2048')
+
+
+STORE_KBLK = 2   # include/omp355.h: OMP_STORE_KBLK
+
+
+def check_table_refusals():
+    """what omp_gemm_bias_act refuses of a per-row table: OMP_ERR_INVALID, a message that names the entry point, every sentinel kept"""
+    out = []
+
+    def refused(c, **change):
+        launch = (lambda call: gpu_launch(dict(call, **change)))
+        out.extend(run_case(c, launch, expect=ERR_INVALID, expect_msg='omp_gemm_bias_act')[0])
+    few = case(0, 'bf16', 'bf16', 64, 64, 128, bias='table', mod=6, off=4)
+    big = case(6, 'bf16', 'bf16', 129, 64, 128, bias='table', mod=6, off=4)
+    refused(few)                                                            # M <= 64, no split-K hint, no forced tile kernel
+    refused(dict(few, sel=3))                                               # ... nor under a forced kernel without the table
+    refused(big, bias_mode='m')                                             # bias_along_m
+    refused(big, trans_rows=43, trans_ld=64)                                # trans_out
+    refused(dict(big, M=128), store_mode=STORE_KBLK, kv=(1, 128, 128, 1, 16))   # a blocked K store
+    refused(big, bias_row_stride=63)                                        # bias_row_stride < N
+    refused(big, bias=None)                                                 # a null bias
+    refused(big, bias_row_off=-1)                                           # a negative bias_row_off
+    refused(big, bias_row_mod=-1)                                           # a negative bias_row_mod
     return out

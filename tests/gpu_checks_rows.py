@@ -395,9 +395,11 @@ def dec_chain(kind, x3, W, pos, vocab=1104, seed=100):
         bod, g2d, b2d, qtd = vd('bo'), vd('g2'), vd('b2'), vd('qtab')
 
         def launch(b):
-            ops.dec_rows_mid(b['att'], b['x'], stream, stride, bod, g2d, b2d, qtd, dpos, q=b['q'], x3=x3, xcd_mask=launch.mask)
+            ops.dec_rows_mid(b['att'], b['x'], stream, stride, bod, g2d, b2d, qtd, dpos, q=b['q'], x3=x3, xcd_mask=launch.mask, pos_mod=launch.pos_mod)
         ch = Chain('mid', eng, base, launch, ('x', 'q'))
         ch.out_shapes = dict(q=(D, odt))
+        launch.pos_mod = 0          # > 0: row r sits at position r % pos_mod and dpos (ch.dpos: the check moves it) is not read
+        ch.dpos = dpos
     else:
         x2 = ref_ffn_body(x, att, W['Wc'], W['bc'], W['g3'], W['b3'], W['W1'], W['b1'], W['W2'], W['bb2'], bf)
         common = dict(out_b=vd('bc'), ln_g=vd('g3'), ln_b=vd('b3'), ff1_b=vd('b1'), ff2_b=vd('bb2'), x3=x3)
@@ -536,6 +538,136 @@ def check_dec_chain(kind, x3=False):
             _sweep(out, ch, '%s auto tile %d' % (tag0, t), (R,), base[t])
     finally:
         ops.rows_tile(0)
+    return out
+
+
+MID_POS_MODS = (1, 2, 6, 7, P)      # P: the largest the check's qtab has rows for
+MID_POS_ROWS = (1, 15, 16, 17, 200, 2049)
+
+
+def ref_mid_rows(W, x, att, pos_of_row):
+    """ref_mid with a position per row (bf16 chains) -> (x', q): row r at position pos_of_row[r]"""
+    x1, q = zip(*[ref_mid(x[r:r + 1], att[r:r + 1], W['Wo'], W['bo'], W['g2'], W['b2'], W['Wq'], W['qtab'], int(pos_of_row[r]), True)
+                  for r in range(x.shape[0])])
+    return torch.cat(x1), torch.cat(q)
+
+
+def one_position_launches(ch, positions):
+    """the one-position form of the mid chain on the NB base rows at every position in `positions`
+    -> (x' [NB, D] of the first, q [len(positions), NB, D], positions whose x' differs from the first's)"""
+    xb, ab = ch.base['x'][0], ch.base['att'][0]
+    q = torch.empty((len(positions), NB, D), dtype=torch.bfloat16, device=DEV)
+    x0, differ = None, torch.zeros((), dtype=torch.int64, device=DEV)
+    ch.launch.pos_mod = 0
+    for i, pos in enumerate(positions):
+        ch.dpos[0] = pos
+        x = xb.clone()
+        ch.launch(dict(att=ab, x=x, q=q[i]))
+        if x0 is None:
+            x0 = x
+        differ += (x.view(torch.int32) != x0.view(torch.int32)).any()
+    torch.cuda.synchronize()
+    return x0, q, int(differ.item())
+
+
+def compare_pos_mod(out, tag, got, probs, src, L, x0, qpos):
+    """row r of a pos_mod = L launch of the base rows src[r] == row src[r] of the one-position launch at position r % L, bit for bit"""
+    pos = torch.arange(src.shape[0], device=src.device) % L
+    bad = [k for k, want in (('x', x0[src]), ('q', qpos[pos, src])) if not torch.equal(got[k], want)]
+    out.append(rec(tag + ': every row == its row of the one-position launch at r %% %d, bit for bit%s' % (L, '' if not bad else ' -- differs: %s' % bad),
+                   len(bad), 0))
+    out.append(rec(tag + ': guard rows untouched, no NaN / inf in valid rows' + ('' if not probs else ' -- %s' % '; '.join(probs)), len(probs), 0))
+
+
+_MID_POS_BASE = []
+
+
+def mid_pos_base():
+    """(weights, chain, base x / att on the host, one-position launches at every position) -- launched once, shared by every pos_mod"""
+    from advancedliteratemachinery_amd import ops
+    if not _MID_POS_BASE:
+        W = _dec_setup(False, 0)
+        ch, _ = dec_chain('mid', False, W, 0)
+        ops.rows_tile(0)
+        _MID_POS_BASE.append((W, ch, ch.base['x'][0].double().cpu(), ch.base['att'][0].double().cpu()) + one_position_launches(ch, list(range(P))))
+    return _MID_POS_BASE[0]
+
+
+def check_dec_mid_pos_mod(L):
+    """omp_dec_rows_args.pos_mod (dec_rows_mid_kernel<RTT, E, ROWPOS>: the batched prompt prefill's form of the mid chain): float64 with a
+    position per row, and bit for bit the one-position launch at each row's position, at the auto tiles (16 rows up to 2048, 32 at 2049) and
+    at every forced tile; d_pos holds a position no row of the launch sits at (it is not read)"""
+    from advancedliteratemachinery_amd import ops
+    out = []
+    W, ch, x_h, att_h, x0, qpos, differ = mid_pos_base()
+    tag0 = 'rows[bf16] mid pos_mod'
+    try:
+        ops.rows_tile(0)
+        out.append(rec(tag0 + ': x is the same at every position 0 .. %d (one-position launches)' % (P - 1), differ, 0))
+        out.append(rec(tag0 + ': auto tile 16 at R = 200, 32 at R = 2049 (got %d, %d)' % (ops.rows_tile_choice(200, True), ops.rows_tile_choice(2049, True)),
+                       int(ops.rows_tile_choice(200, True) != 16) + int(ops.rows_tile_choice(2049, True) != 32), 0))
+        ch.launch.pos_mod = L
+        ch.dpos[0] = P - 3 if L < P else 0        # not a position of this launch (L = P: every position is one; row 0's then)
+        tag = '%s=%d' % (tag0, L)
+        # float64: the NB base rows in order, row r at position r % L
+        got, probs = ch.run(NB)
+        rx, rq = ref_mid_rows(W, x_h, att_h, [r % L for r in range(NB)])
+        _gate(out, tag + ' R=%d x vs float64 (per-row relative)' % NB, got['x'], rx, ('bf16', 'mid', 'x'))
+        _gate(out, tag + ' R=%d q vs float64 (per-row relative)' % NB, got['q'], rq, ('bf16', 'mid', 'q'))
+        compare_pos_mod(out, tag + ' R=%d' % NB, got, probs, torch.arange(NB, device=DEV), L, x0, qpos)
+        for R in MID_POS_ROWS:
+            src = src_map(R)
+            got, probs = ch.run(R, src)
+            compare_pos_mod(out, '%s R=%d auto tile %d' % (tag, R, ops.rows_tile_choice(R, True)), got, probs, src, L, x0, qpos)
+        for rtt in (2, 3, 4, 5):
+            ops.rows_tile(rtt)
+            src = src_map(4097, 37, 101)
+            got, probs = ch.run(4097, src)
+            compare_pos_mod(out, '%s R=4097 tile %d (forced)' % (tag, 16 * rtt), got, probs, src, L, x0, qpos)
+        ops.rows_tile(0)
+        if L != 6:
+            return out
+        # the masked grid
+        ch.launch.pos_mod = 6
+        src = src_map(200)
+        plain, _ = ch.run(200, src)
+        ch.launch.mask = 0x0F
+        got, probs = ch.run(200, src)
+        same = all(torch.equal(got[k], plain[k]) for k in got)
+        out.append(rec(tag0 + '=6 R=200: xcd_mask 0x0F == unmasked, bit for bit%s' % ('' if not probs else ' -- ' + '; '.join(probs)), (0 if same else 1) + len(probs), 0))
+        compare_pos_mod(out, tag0 + '=6 R=200 xcd_mask 0x0F', got, probs, src, 6, x0, qpos)
+    finally:
+        ch.launch.mask, ch.launch.pos_mod = 0, 0
+        ops.rows_tile(0)
+    return out
+
+
+def check_dec_mid_pos_mod_refusals():
+    """pos_mod < 0, and pos_mod with the split-pair chain: OMP_ERR_INVALID, x keeps its bits and q its sentinels"""
+    out = []
+    for x3, pos_mod in ((False, -1), (True, 6), (True, -1)):
+        ch, _ = dec_chain('mid', x3, _dec_setup(x3, 0), 0)
+        inner, err = ch.launch, []
+
+        def launch(b):
+            try:
+                inner(b)
+            except RuntimeError as e:
+                err.append(str(e))
+        inner.pos_mod = pos_mod
+        ch.launch = launch
+        R = 200
+        src = src_map(R)
+        got, probs = ch.run(R, src)
+        probs = [p for p in probs if 'valid row holds NaN' not in p]       # q keeps its sentinel, a NaN payload
+        name = 'rows[%s] mid pos_mod=%d' % (ch.eng, pos_mod)
+        ok = len(err) == 1 and '(-22)' in err[0] and 'omp_dec_rows_mid: pos_mod' in err[0]
+        out.append(rec(name + ': refused with -22%s' % ('' if ok else ' -- %s' % (err or 'no error')), 0 if ok else 1, 0))
+        qi = got['q'].view(torch.int32 if got['q'].dtype == torch.float32 else torch.int16)
+        kept = bool((qi == (F32_SENT if got['q'].dtype == torch.float32 else BF16_GUARD)).all().item()) and \
+            torch.equal(got['x'].view(torch.int32), ch.base['x'][0][src].view(torch.int32))
+        out.append(rec(name + ': nothing written (x its bits, q its sentinels, guard rows)%s' % ('' if not probs else ' -- ' + '; '.join(probs)),
+                       (0 if kept else 1) + len(probs), 0))
     return out
 
 

@@ -1,7 +1,9 @@
 """The float64 restatements of omp_gemm_bias_act (tests/gpu_checks_gemm.py: ref_gemm, ref_ln_gemm) against plain torch (F.linear, F.gelu,
 F.layer_norm) and against tests/fake_ops.gemm, and the checker of the GPU tests (run_case) against a fake launch built on fake_ops.gemm
 with ONE seeded defect at a time: each defect must yield a failing record of the kind that is there to catch it, and the clean fake none
--- a checker that cannot fail proves nothing about the kernels.  CPU only."""
+-- a checker that cannot fail proves nothing about the kernels.  The bias table's per-row form (bias 'table': bias_row_mod / bias_row_off)
+has its own pins and its own four seeded defects, each of which must fail the float64 gate AND the bit gate against the one-row form.
+CPU only."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -115,7 +117,18 @@ def fake_launch(defect=None):
             bias = bias[int(c['bias_row'].item())]
         if defect == 'bias_along_m dropped' and c['bias_mode'] == 'm':
             bias = None
-        y = fake_ops.gemm(A, W, bias, act=c['act'], bias_along_m=c['bias_mode'] == 'm', out_dtype=torch.float32)
+        mod, off = c['bias_row_mod'], c['bias_row_off']
+        if bias is not None and c['bias_mode'] == 'table' and mod == 0:     # the one-row form on the per-row cases' table
+            bias = bias[int(c['bias_row'].item())]
+        if mod > 0 and defect in TABLE_DEFECTS:
+            rows = {'table: off dropped': torch.arange(M) % mod, 'table: every row takes row off': torch.full((M,), off % mod),
+                    'table: shifted by one': (off + torch.arange(M) + 1) % mod, 'table: ragged N keeps the column bias': (off + torch.arange(M)) % mod}[defect]
+            bias = bias[rows].clone()
+            if defect == 'table: ragged N keeps the column bias':          # the 16-byte chunk that straddles N: bias[n], which is table row 0
+                ch = 16 // c['out'].element_size()
+                bias[:, N // ch * ch:] = c['bias'][0, N // ch * ch:]
+            mod, off = M, 0
+        y = fake_ops.gemm(A, W, bias, act=c['act'], bias_along_m=c['bias_mode'] == 'm', out_dtype=torch.float32, bias_row_mod=mod, bias_row_off=off)
         if c['out2'] is not None:
             c['out2'].copy_(y.to(c['out2'].dtype))
         if c['residual'] is not None:
@@ -151,6 +164,17 @@ CASES = [
 # defect -> the kind of record that must fail
 DEFECTS = {'bias_along_m dropped': 'value', 'last K tile skipped': 'value', 'gap column': 'guards', 'guard row': 'guards',
            'reads row M': 'nan', 'row M-1 from row M-2': 'value'}
+# the per-row bias table: defect -> what it does; each must fail the float64 gate of run_case AND the bit gate against the one-row form
+TABLE_DEFECTS = ('table: off dropped', 'table: every row takes row off', 'table: shifted by one', 'table: ragged N keeps the column bias')
+TABLE_CASES = [
+    G.case(6, 'bf16', 'bf16', 65, 67, 128, bias='table', mod=6, off=4),
+    G.case(6, 'bf16', 'fp32', 129, 67, 128, bias='table', mod=7, off=10, inplace=True, pitch='scalar'),
+    G.case(5, 'bf16', 'split', 129, 136, 128, bias='table', mod=6, off=4, act=G.ACT_GELU),
+    G.case(5, 'fp32', 'fp32', 129, 131, 64, bias='table', mod=2, off=5, res=True),
+    G.case(5, 'bf16', 'bf16', 257, 136, 128, bias='table', mod=7, off=10, res=True, c2=True),
+    G.case(4, 'bf16', 'fp32', 17, 20, 128, bias='table', mod=6, off=4, rows=64, tail=64, hint=True),
+    G.case(4, 'fp32', 'fp32', 49, 20, 64, bias='table', mod=7, off=10, ln=1e-5, rows=64, tail=64, hint=True),
+]
 # what the fp32 test double itself is off by, relative to a row's max |ref|, per destination: its float summation (K <= 512), one bf16
 # rounding of the result (2^-8 of the element, twice where a rounding flips), the 16 mantissa bits of a pair row
 FAKE_REL = {'fp32': 1e-5, 'bf16': 2.0 ** -7, 'split': 2.0 ** -15}
@@ -233,3 +257,87 @@ def test_shapes_follow_the_kernels():
     assert [k // 4 for k in G.LN_K['bf16']] == [32, 96, 128, 256] and G.LN_K['fp32'][0] == 64
     for sel, T in G.TILE.items():
         assert all(G.accepts(G.case(sel, 'bf16', 'bf16', 2 * T, 2 * T, nt * 64)) for nt in G.K_TILES[sel]), sel
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the bias table's per-row form
+# ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('act', [G.ACT_NONE, G.ACT_GELU, G.ACT_RELU])
+@pytest.mark.parametrize('mod,off', [(1, 4), (2, 5), (6, 4), (7, 10), (7, 0)])
+def test_ref_gemm_table_is_linear_plus_the_row_of_the_table(mod, off, act):
+    M, N, K = 37, 29, 96
+    A, W, res, tab = _r(M, K, seed=1), _r(N, K, seed=2, s=K ** -0.5), _r(M, N, seed=3), _r(mod, N, seed=4)
+    y = torch.stack([F.linear(A[m], W, tab[(off + m) % mod]) for m in range(M)])
+    y = F.gelu(y) if act == G.ACT_GELU else (F.relu(y) if act == G.ACT_RELU else y)
+    assert _rel(G.ref_gemm(A, W, tab, 'table', act, res, mod=mod, off=off), y + res) < TOL
+    # and fake_ops.gemm states the same
+    fake = fake_ops.gemm(A.float(), W.float(), tab.float(), residual=res.float(), act=act, bias_row_mod=mod, bias_row_off=off, out_dtype=torch.float32)
+    assert _rel(fake.double(), y + res) < 2e-6
+
+
+def test_table_offsets_tell_the_formulas_apart():
+    """off is no multiple of mod and M >= 2 mod + 1 in the cases the checks run: the four formulas of TABLE_DEFECTS give other rows"""
+    for mod in G.TABLE_MODS[1:]:
+        assert G.table_offs(mod)[0] == 0 and G.table_offs(mod)[1] == 4 and G.table_offs(mod)[2] % mod   # mod + 3: never a multiple
+    for (mod, off) in G.TABLE_TILE_MODS:
+        assert mod == 1 or off % mod
+        assert all(M >= 2 * mod + 1 for sel in (5, 6) for M in G.TABLE_TILE_SHAPES[sel][0])
+    assert G.PTABLE_ROWS == max(G.TABLE_MODS)
+
+
+@pytest.mark.parametrize('c', TABLE_CASES, ids=G.tag)
+def test_clean_fake_passes_both_table_gates(c):
+    records = G.run_table(c, fake_launch(), 'cpu')
+    bad = [r for r in records if not r['ok'] and r['kind'] in ('guards', 'nan', 'launch', 'cap', 'bits')]
+    assert not bad, bad
+    assert sum(r['kind'] == 'bits' for r in records) == (2 if c['c2'] else 1)
+    rel = [float(r['note'].split('rel ')[1]) for r in records if 'rel ' in r['note']]
+    assert rel and max(rel) <= FAKE_REL[c['out']], rel
+
+
+@pytest.mark.parametrize('defect', TABLE_DEFECTS)
+def test_seeded_table_defect_fails_both_gates(defect):
+    hit = 0
+    for c in TABLE_CASES:
+        if 'ragged' in defect and (c['sel'] == 4 or c['N'] % 8 == 0):   # the 4-value path of the tile kernels at a ragged N edge
+            continue
+        records = G.run_table(c, fake_launch(defect), 'cpu')
+        kinds = {r['kind'] for r in records if not r['ok']}
+        assert 'bits' in kinds and ({'value', 'cap'} & kinds), (G.tag(c), defect, [r for r in records if not r['ok']])
+        assert 'guards' not in kinds and 'nan' not in kinds, (G.tag(c), kinds)
+        hit += 1
+    assert hit >= 3
+
+
+def test_table_guard_rows_are_nan():
+    """a launch that reads the row behind the table (mod taken one too large) is seen by value: the NaN record fails"""
+    c = TABLE_CASES[0]
+
+    def launch(call):
+        tab = _beyond(call['bias'], c['mod'] + 1, c['N'])
+        fake_launch()(dict(call, bias=tab, bias_row_mod=c['mod'] + 1))
+    kinds = {r['kind'] for r in G.run_case(c, launch, 'cpu', report=False)[0] if not r['ok']}
+    assert 'nan' in kinds
+
+
+def test_ln_inputs_stay_clear_of_bf16_ties():
+    """ln_resolvable: a normalised element on a bf16 rounding tie (to fp32 resolution) is seen where its flip matters, next to the tie
+    not, nor where the flip is negligible against the row's largest output; the seeds the per-row table sweep draws its LayerNorm rows from exist, pass, and
+    seed 16 -- one element 3e-8 from a tie -- is passed over"""
+    K = 128
+    lo = torch.tensor(1.5, dtype=torch.bfloat16)
+    hi = (lo.view(torch.int16) + 1).view(torch.bfloat16)
+    tie = ((lo.double() + hi.double()) / 2).item()
+    W = _r(16, K, seed=3, s=K ** -0.5)
+    X = torch.ones(1, K)                       # a constant row normalises to beta exactly
+    for delta, ok in ((0.0, False), (3e-8, False), (-5e-7, False), (1e-5, True), (-1e-5, True)):
+        assert G.ln_resolvable(X, torch.ones(K), torch.full((K,), tie * (1 + delta), dtype=torch.float64), 1e-5, W) == ok, delta
+    Wbig = torch.cat([W, torch.full((1, K), 40.0, dtype=torch.float64)])           # a row max the flip cannot move: it does not count
+    assert G.ln_resolvable(X, torch.ones(K), torch.full((K,), tie, dtype=torch.float64), 1e-5, Wbig * torch.cat([torch.full((16, 1), 1e-3, dtype=torch.float64), torch.ones(1, 1, dtype=torch.float64)]))
+    for N in (16, 20, 512):
+        seed = G.ln_seed('bf16', N, K, 1e-5, N)
+        assert seed % 1000 == N and G.ln_seed('fp32', N, 64, 1e-5, N) == N
+        h = G.host('bf16', 64, N, K, 0, seed, True)
+        assert G.ln_resolvable(h['A'], h['g'], h['b'], 1e-5, h['W'])
+    h = G.host('bf16', 64, 16, K, 0, 16, True)
+    assert not G.ln_resolvable(h['A'], h['g'], h['b'], 1e-5, h['W']) and G.ln_seed('bf16', 16, K, 1e-5, 16) != 16

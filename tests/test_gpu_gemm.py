@@ -1,7 +1,8 @@
 """GPU tests of omp_gemm_bias_act (csrc/gemm.hip, gemm256.hip, gemm4w.hip, gemm4wr.hip, gemm4wp.hip) at every ragged edge, pitch and few-row count: sentinel-guarded destinations,
 NaN-guarded operands, every K-tile count around each ring depth, every epilogue on vector and scalar pitches, bit equality of the 256x256
 kernels with the 128x128 kernel, every M from 1 to 64 through gemm_rows and gemm_small, the fused LayerNorm prologue with planted rows and
-two eps values, in place against out of place, clean refusals (tests/gpu_checks_gemm.py)."""
+two eps values, in place against out of place, clean refusals; the bias table's per-row form (bias_row_mod / bias_row_off) through selectors
+4, 5 and 6 against float64 and, bit for bit, against the one-row form of each table row (tests/gpu_checks_gemm.py)."""
 import pytest
 import torch
 
@@ -76,3 +77,24 @@ def test_few_rows_epilogues(G, sel, dtn):
 def test_layernorm_prologue(G, dtn, K):
     assert K in G.LN_K[dtn]
     _assert_all(G.check_ln(dtn, K))
+
+
+# the bias table's per-row form (bias_row_mod / bias_row_off): float64 and bit equality with the one-row form
+@pytest.mark.parametrize('ln', [False, True], ids=['plain', 'ln'])
+@pytest.mark.parametrize('dtn,out', [('bf16', 'bf16'), ('bf16', 'fp32'), ('fp32', 'fp32')])
+def test_table_bias_small(G, dtn, out, ln):
+    _assert_all(G.check_table_small(dtn, out, ln))
+
+
+@pytest.mark.parametrize('sel,N', [(6, 64), (6, 72), (6, 67), (5, 128), (5, 136), (5, 131)])
+def test_table_bias_tile(G, sel, N):
+    assert N in G.TABLE_TILE_SHAPES[sel][1]
+    _assert_all(G.check_table_tile(sel, N))
+
+
+def test_table_bias_four_stage_ring(G):
+    _assert_all(G.check_table_ring4())
+
+
+def test_table_bias_refusals(G):
+    _assert_all(G.check_table_refusals())

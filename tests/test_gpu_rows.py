@@ -1,6 +1,6 @@
 """GPU tests of the row-owner chains at every row count, tile and grid the engine launches: float64 on 256 distinct base rows (edge rows
 included), every row of every larger launch bit-identical to its source row, guard rows, determinism, XCD masks, the memory projection in
-full (tests/gpu_checks_rows.py)."""
+full, the mid chain with a position per row (pos_mod) against the one-position launches (tests/gpu_checks_rows.py)."""
 import pytest
 import torch
 
@@ -50,3 +50,13 @@ def test_kv_rows_full(C):
 
 def test_kv_rows_batch(C):
     _assert_all(C.check_kv_rows_batch())
+
+
+@pytest.mark.parametrize('pos_mod', [1, 2, 6, 7, 1024])
+def test_dec_rows_mid_pos_mod(C, pos_mod):
+    assert pos_mod in C.MID_POS_MODS and C.P == 1024
+    _assert_all(C.check_dec_mid_pos_mod(pos_mod))
+
+
+def test_dec_rows_mid_pos_mod_refusals(C):
+    _assert_all(C.check_dec_mid_pos_mod_refusals())

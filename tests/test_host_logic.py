@@ -612,6 +612,100 @@ def test_gemm_dispatch_table():
         G(128, 512, 100)
 
 
+def test_gemm_dispatch_of_the_per_row_bias_table():
+    """bias_row_mod > 0 (the batched prompt prefill's products) lives in the epilogues of gemm_small and gemm_dma only: launch_gemm
+    reroutes every other selector, forced or chosen, to 64x64 below 256 tiles of 128x128 and to 128x128 from there; forced 5 and 6
+    stay; the LayerNorm prologue and the split-K hint at M <= 64 answer 4; few rows without the hint have no kernel (-22)."""
+    import ctypes
+    from advancedliteratemachinery_amd import _lib, ops
+
+    def choice(M, N, K, mod=6, off=4, ln=False, small_m=False, base=1 << 20):
+        a = _lib.GemmArgs()
+        a.A, a.lda, a.W, a.ldw = base, K, base + (1 << 30), K
+        a.bias, a.bias_row_stride, a.bias_row_mod, a.bias_row_off = base + (2 << 30), N, mod, off
+        a.C, a.ldc, a.M, a.N, a.K = base + (4 << 30), N, M, N, K
+        a.dtype, a.out_dtype = ops.OMP_BF16, ops.OMP_BF16
+        if ln:
+            a.ln_gamma, a.ln_beta, a.ln_eps = base + (5 << 30), base + (6 << 30), 1e-5
+        a.small_m_splitk = 1 if small_m else 0
+        rc = _lib.lib().omp_debug_gemm_choice(ctypes.byref(a))
+        if rc < 0:
+            _lib.check(rc, 'omp_debug_gemm_choice')
+        return rc
+    few_tiles, at_256, below_256 = (300, 384, 256), (2048, 2048, 256), (2048 - 128, 2048, 256)   # 9, 256 and 240 tiles of 128x128
+    assert ops.gemm_choice(10240, 1536, 512) == 9 and choice(10240, 1536, 512) == 5        # auto picks 9 without the table
+    assert ops.gemm_choice(420, 1536, 512) == 6 and choice(420, 1536, 512) == 6            # the pass at R = 70, n_prompt 7
+    assert choice(1025, 2048, 512) == 6 and choice(321 * 6, 2048, 512) == 5                # 4-deep ring / 128x128 inside a pass
+    try:
+        for forced in (0, 3, 9, 10, 16, 20):
+            ops.force_gemm_kernel(forced)
+            assert choice(*few_tiles) == 6 and choice(*below_256) == 6 and choice(*at_256) == 5, forced
+            assert choice(2048, 2048, 256, mod=0) == (forced or 5), forced                 # without the table the forced selector holds
+            with pytest.raises(RuntimeError, match=r'omp_gemm_bias_act: unknown kernel selector -1'):
+                choice(64, 512, 512)     # few rows, no hint: no kernel for the table (a launch answers -22: tests/test_gpu_gemm.py)
+        for forced in (5, 6):
+            ops.force_gemm_kernel(forced)
+            assert choice(*few_tiles) == forced and choice(*at_256) == forced and choice(64, 512, 512) == forced
+        ops.force_gemm_kernel(0)
+        assert choice(64, 512, 512, small_m=True) == 4 and choice(1, 1536, 512, small_m=True) == 4
+        assert choice(32, 1536, 512, ln=True) == 4 and choice(64, 1536, 512, ln=True, small_m=True) == 4
+        assert all(choice(M, N, 128, small_m=True) == 4 for M in (1, 16, 17, 64) for N in (16, 20, 512))   # the shapes tests/gpu_checks_gemm.py sweeps unforced
+        ops.force_gemm_kernel(6)
+        assert choice(32, 1536, 512, ln=True) == 4                                         # the prologue wins over a forced selector
+    finally:
+        ops.force_gemm_kernel(0)
+
+
+def prefill_paths(R, n_prompt):
+    """(pass, step): the kernels the batched prompt prefill of R plan rows and its stepwise twin run, read from the host logic
+    (omp_debug_gemm_choice with the products' own arguments, ops.rows_tile_choice): selector and ring depth of the q|k|v product (per-row
+    bias table in the pass), the attention out-projections (fp32 residual in place), linear1 (ReLU) and linear2, and the mid chain's tile"""
+    import ctypes
+    from advancedliteratemachinery_amd import _lib, ops
+
+    def sel(M, N, K, mod=0, out=ops.OMP_BF16, res=False, act=0, base=1 << 20):
+        a = _lib.GemmArgs()
+        a.A, a.lda, a.W, a.ldw, a.bias = base, K, base + (1 << 30), K, base + (2 << 30)
+        a.bias_row_stride, a.bias_row_mod = (N, mod) if mod else (0, 0)
+        a.C, a.ldc, a.M, a.N, a.K, a.act = base + (4 << 30), N, M, N, K, act
+        a.residual, a.ldr = (a.C, N) if res else (None, 0)
+        a.dtype, a.out_dtype, a.small_m_splitk = ops.OMP_BF16, out, 1
+        rc = _lib.lib().omp_debug_gemm_choice(ctypes.byref(a))
+        assert rc > 0, rc
+        ring = '' if rc != 6 else ('/ring8' if -(-M // 64) * -(-N // 64) <= 512 else '/ring4')
+        return '%d%s' % (rc, ring)
+    L = n_prompt - 1
+    return tuple(dict(qkv=sel(M, 1536, 512, mod), out=sel(M, 512, 512, out=ops.OMP_F32, res=True), ff1=sel(M, 2048, 512, act=ops.ACT_RELU),
+                      ff2=sel(M, 512, 2048, out=ops.OMP_F32, res=True), mid=ops.rows_tile_choice(M, True)) for M, mod in ((R * L, L), (R, 0)))
+
+
+def test_prefill_limits_reach_the_other_tile_kernels():
+    """The row counts tests/test_gpu_prefill.py runs the pass at, and what they reach that R = 70 does not: the 4-deep ring of the
+    64x64 kernel (R = 200), the 128x128 kernel for linear1 (R = 321, n_prompt 34 / 42) and for the per-row q|k|v product (R = 682,
+    R = 70 at n_prompt 42), the mid chain's 32-row tile (R = 682, n_prompt 34 / 42) -- while the step stays on 64x64 / ring8 and the
+    16-row tile throughout.  Host logic only."""
+    from advancedliteratemachinery_amd.model.transformer import Decoder
+    step = dict(qkv='6/ring8', out='6/ring8', ff1='6/ring8', ff2='6/ring8', mid=16)
+    few = dict(qkv='4', out='4', ff1='4', ff2='4', mid=16)                 # 64 plan rows: the split-K small-M kernel on both sides
+    want = {
+        (70, 7): dict(qkv='6/ring8', out='6/ring8', ff1='6/ring8', ff2='6/ring8', mid=16),
+        (128, 7): dict(qkv='6/ring8', out='6/ring8', ff1='6/ring8', ff2='6/ring8', mid=16),
+        (129, 7): dict(qkv='6/ring8', out='6/ring8', ff1='6/ring8', ff2='6/ring8', mid=16),
+        (200, 7): dict(qkv='6/ring8', out='6/ring8', ff1='6/ring4', ff2='6/ring8', mid=16),
+        (321, 7): dict(qkv='6/ring4', out='6/ring8', ff1='5', ff2='6/ring8', mid=16),
+        (682, 7): dict(qkv='5', out='6/ring8', ff1='5', ff2='6/ring8', mid=32),
+        (1023, 3): dict(qkv='6/ring4', out='6/ring8', ff1='5', ff2='6/ring8', mid=16),
+        (70, 34): dict(qkv='6/ring4', out='6/ring8', ff1='5', ff2='6/ring8', mid=32),
+        (70, 42): dict(qkv='5', out='6/ring8', ff1='5', ff2='6/ring8', mid=32),
+    }
+    for (R, n_prompt), w in want.items():
+        p, s = prefill_paths(R, n_prompt)
+        assert (p, s) == (w, step), (R, n_prompt, p, s)
+        assert Decoder.PREFILL_MIN_ROWS <= R < 1024 and R * (n_prompt - 1) <= Decoder.PREFILL_MAX_ROWS
+    assert prefill_paths(64, 34)[1] == few and prefill_paths(64, 42)[1] == few
+    assert 683 * 6 > Decoder.PREFILL_MAX_ROWS >= 682 * 6 and Decoder.PREFILL_MAX_ROWS >= 1023 * 2   # R = 683 at n_prompt 7 stays stepwise
+
+
 def test_gemm_choice_grid_matches_the_record():
     """The whole dispatch table of csrc/gemm.hip (GEMM_SELECTORS, gemm_auto_select, gemm_accepts and the argument checks in front of them) replayed
     over the grid of tools/gemm_choice_grid.py -- every forced selector x dtype pair x store mode, 8.3 M cells in 304 blocks -- against

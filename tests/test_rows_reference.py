@@ -163,3 +163,38 @@ def test_rounding_switch():
     assert y.var(unbiased=False).item() < 1e-12
     y2 = xs[2] + R._vec(4, d)
     assert y2.var(unbiased=False).item() < R.EPS
+
+
+def test_pos_mod_comparison_notices_a_launch_at_one_position():
+    """compare_pos_mod (the mid chain with a position per row, tests/gpu_checks_rows.py): exact on a fake launch that gives row r its row of
+    the one-position result at r % L; failing when every row got *d_pos, whatever L -- the check parks d_pos at a position no row sits at --
+    and when the position is taken from the source row instead of the launch's row.  ref_mid_rows is ref_mid row by row."""
+    NB, Pn = R.NB, 9
+    W = {k: _r(d, d, seed=i, s=d ** -0.5) for i, k in enumerate(('Wo', 'Wq'))}
+    W.update(bo=_r(d, seed=3, s=0.1), g2=1 + _r(d, seed=4, s=0.1), b2=_r(d, seed=5, s=0.1), qtab=_r(Pn, d, seed=6, s=0.3))
+    x, att = _r(NB, d, seed=7), _r(NB, d, seed=8).to(torch.bfloat16).double()
+    per_pos = [R.ref_mid(x, att, W['Wo'], W['bo'], W['g2'], W['b2'], W['Wq'], W['qtab'], p, True) for p in range(Pn)]
+    x0 = per_pos[0][0].float()
+    qpos = torch.stack([q.to(torch.bfloat16) for _, q in per_pos])
+    rx, rq = R.ref_mid_rows(W, x[:20], att[:20], [r % 7 for r in range(20)])
+    assert _rel(rx, per_pos[0][0][:20]) < TOL
+    assert all(torch.equal(rq[r], per_pos[r % 7][1][r]) for r in range(20))
+    assert not torch.equal(rq[1], per_pos[0][1][1])
+    for L in (1, 2, 6, 7):
+        for Rn in (1, 17, 200, 300):
+            src = (torch.arange(Rn) * 101 + 13) % NB
+            pos = torch.arange(Rn) % L
+            ok = lambda got: all(r['ok'] for r in _cmp(got, src, L, x0, qpos))      # noqa: E731
+            assert ok(dict(x=x0[src], q=qpos[pos, src]))
+            assert not ok(dict(x=x0[src], q=qpos[torch.full((Rn,), Pn - 1), src]))                 # *d_pos for every row
+            if L > 1 and Rn > 1:
+                assert not ok(dict(x=x0[src], q=qpos[torch.zeros(Rn, dtype=torch.int64), src]))    # ... at d_pos = 0
+            if L > 1 and Rn > L:
+                assert not ok(dict(x=x0[src], q=qpos[src % L, src]))                               # the source row's index, not the launch's
+            assert not ok(dict(x=x0[src] + 1e-3, q=qpos[pos, src]))
+
+
+def _cmp(got, src, L, x0, qpos):
+    out = []
+    R.compare_pos_mod(out, 'fake', got, [], src, L, x0, qpos)
+    return out
