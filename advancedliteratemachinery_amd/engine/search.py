@@ -1,5 +1,6 @@
-"""Page search on records: where a phrase stands on a read page, which words carry it and how badly it was misread (DESIGN.md section 25;
-utils/page_search.py holds the definition, csrc/page_search.hip the kernel)."""
+"""Page search on records: where a phrase (find_text: DESIGN.md section 25, utils/page_search.py, csrc/page_search.hip) or a shape such as a
+date, an amount or an id (find_pattern: DESIGN.md section 29, utils/page_pattern.py, csrc/page_pattern.hip) stands on a read page, which
+words carry it and how badly it was misread."""
 import numpy as np
 
 
@@ -19,6 +20,23 @@ def _box(records):
         return None
     xs, ys = [float(p[0]) for p in pts], [float(p[1]) for p in pts]
     return (min(xs), min(ys), max(xs), max(ys))
+
+
+def _carried(recs, text, w_start, w_end, rows):
+    """the (end, dist, start) rows of one job -> (the hits that touch a word, as dicts with the words that carry them; how many touch
+    none).  first is the first word with word_start + word_len > start, last the last word with word_start < end."""
+    hits, dropped = [], 0
+    for e, d, s in np.asarray(rows).tolist():
+        if e < 0:
+            break
+        first = int(np.searchsorted(w_end, s, side='right'))               # the first word with word_start + word_len > start
+        last = int(np.searchsorted(w_start, e, side='left')) - 1          # the last word with word_start < end
+        if first > last:
+            dropped += 1
+            continue
+        carried = recs[first:last + 1]
+        hits.append(dict(dist=d, chars=(s, e), text=text[s:e], words=(first, last), records=carried, box=_box(carried)))
+    return hits, dropped
 
 
 def find_text(records, queries, field='rec', max_dist=None, max_ratio=0.2, sep=' ', normalise=str.casefold, max_hits=16, searcher=None,
@@ -66,18 +84,65 @@ def find_text(records, queries, field='rec', max_dist=None, max_ratio=0.2, sep='
         w_end = w_start + w_len
         for q in qs:
             dist, end = (int(v) for v in res['best'][at])
-            hits, dropped = [], 0
-            for e, d, s in res['hits'][at].tolist():
-                if e < 0:
-                    break
-                first = int(np.searchsorted(w_end, s, side='right'))           # the first word with word_start + word_len > start
-                last = int(np.searchsorted(w_start, e, side='left')) - 1      # the last word with word_start < end
-                if first > last:
-                    dropped += 1
-                    continue
-                carried = records[b][first:last + 1]
-                hits.append(dict(dist=d, chars=(s, e), text=text[s:e], words=(first, last), records=carried, box=_box(carried)))
+            hits, dropped = _carried(records[b], text, w_start, w_end, res['hits'][at])
             out[b].append(dict(query=q, normalised=names[jobs[at][1]], k=k[jobs[at][1]], best=None if end == 0 else dist, n_hits=int(res['n_hits'][at]),
                                dropped=dropped, hits=hits))
             at += 1
+    return out
+
+
+def find_pattern(records, patterns, field='rec', max_dist=None, max_ratio=0.0, sep=' ', normalise=None, rep_max=None, max_hits=16, searcher=None,
+                 device=None):
+    """records: as find_text takes them, IN THE ORDER TO BE READ.  patterns: a list for all images, or one list (not tuple) per image; a
+    pattern is a string in the syntax of utils.page_pattern.parse_pattern (character classes with ?, {n} and {a,b}; `*` and `+` repeat up to
+    rep_max and are refused without it) or a (name, string) tuple.  Every image becomes one text (page_index); `normalise` is applied to
+    the page words ONLY, never to a pattern, and defaults to None because patterns are case-sensitive shapes.  A pattern with Mand
+    mandatory positions gets the tolerance k = utils.page_pattern.tolerance(Mand, max_dist, max_ratio); max_ratio defaults to 0, exact
+    shapes, and errors are opt-in.  Both defaults are choices that no data set has tested.
+    searcher: a utils.page_pattern.PatternSearcher, or anything with its `run` (HostPatternSearcher: the specification); default: one on
+    `device` (default 'cuda').  All images and patterns go through ONE searcher.run.
+    -> per image a list with one dict per pattern: pattern (the string), name (None for a bare string), P, k, best (the least distance of
+    the pattern against any stretch of the text; None when nothing is within k), n_hits, dropped, hits.  A hit is find_text's dict
+    (dist, chars, text, words, records, box), with one difference: chars starts at the LEAST start that attains dist, the longest match
+    (`\\d{1,4}` in `12345` is `2345`, not `5`), where find_text reports the shortest.  A hit that touches no word is dropped and counted."""
+    from ..utils import page_pattern as PP
+    from ..utils.page_search import page_index
+    records = [list(recs) for recs in records]
+    for b, recs in enumerate(records):
+        for r in recs:
+            if not isinstance(r, dict) or 'polys' not in r:
+                raise ValueError('image %d: find_pattern needs text-spotting records (dicts with `polys`)' % b)
+    patterns = list(patterns)
+    if patterns and all(isinstance(p, list) for p in patterns):            # a tuple is a (name, string) pair, so per-image lists are LISTS
+        if len(patterns) != len(records):
+            raise ValueError('patterns holds %d lists for %d images' % (len(patterns), len(records)))
+        lists = [list(p) for p in patterns]
+    else:
+        lists = [patterns] * len(records)
+    pages = [page_index(recs, field, sep, normalise) for recs in records]
+    table, parsed, k, jobs, named = {}, [], [], [], []
+    for b, ps in enumerate(lists):
+        for p in ps:
+            name, src = (None, p) if isinstance(p, str) else p if isinstance(p, tuple) and len(p) == 2 else (None, None)
+            if not isinstance(src, str) or not (name is None or isinstance(name, str)):
+                raise ValueError('a pattern is a string or a (name, string) pair, got %r' % (p,))
+            if src not in table:
+                table[src] = len(table)
+                parsed.append(PP.parse_pattern(src, rep_max))
+                k.append(PP.tolerance(parsed[-1].Mand, max_dist, max_ratio))
+            jobs.append((b, table[src]))
+            named.append((name, src))
+    out = [[] for _ in records]
+    if not jobs:
+        return out
+    pool, page_off, page_len, masks, opt, pat_len, _ = PP.encode_patterns([p[0] for p in pages], parsed)
+    if searcher is None:
+        searcher = PP.PatternSearcher('cuda' if device is None else device)
+    res = searcher.run(pool, page_off, page_len, masks, opt, pat_len, np.asarray(jobs, dtype=np.int32), np.asarray(k, dtype=np.int32), int(max_hits))
+    for at, ((b, q), (name, src)) in enumerate(zip(jobs, named)):
+        text, w_start, w_len = pages[b]
+        dist, end = (int(v) for v in res['best'][at])
+        hits, dropped = _carried(records[b], text, w_start, w_start + w_len, res['hits'][at])
+        out[b].append(dict(pattern=src, name=name, P=parsed[q].P, k=k[q], best=None if end == 0 else dist, n_hits=int(res['n_hits'][at]), dropped=dropped,
+                           hits=hits))
     return out

@@ -1011,6 +1011,47 @@ def page_search(pool, pool_bytes, page_off, page_len, query_off, query_len, k, j
     return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
 
 
+PAGE_PATTERN_CHUNK = 128       # omp_page_pattern_search: text columns per lane (csrc/page_pattern.hip: PP_CHUNK)
+PAGE_PATTERN_HIT_BYTES = 512    # omp_page_pattern_search: scratch per job and kept hit: 64 lanes x (end, dist)
+
+
+def page_pattern_scratch_bytes(n_jobs, max_hits):
+    """the scratch omp_page_pattern_search needs for n_jobs jobs at max_hits: per job and lane a list of max_hits (end, dist) pairs,
+    whatever the pages' lengths (the entry point checks this size before it launches)"""
+    return max(int(n_jobs), 0) * max(int(max_hits), 0) * PAGE_PATTERN_HIT_BYTES
+
+
+def page_pattern_search(pool, pool_bytes, page_off, page_len, masks, opt, pat_len, k, jobs, sigma, max_hits, scratch, best=None, n_hits=None, hits=None):
+    """omp_page_pattern_search (csrc/page_pattern.hip; utils/page_pattern.py holds the specification): pool uint8 with pool_bytes valid
+    codes, page_off / page_len int32 [P], masks int64 [Q, sigma + 1] (the 64-bit class words: bit i of masks[q, c] says that code c is in
+    the class of position i; row sigma is read as 0), opt int64 [Q] (bit i: position i is optional), pat_len / k int32 [Q], jobs int32
+    [J, 2] = (page, pattern), scratch uint8 with at least page_pattern_scratch_bytes(J, max_hits) bytes -> (best int32 [J, 2] = (dist,
+    end), n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, dist, start), -1 where there is no hit); n_hits = -1 for a job whose
+    lengths, ranges, opt word or tolerance are out of bounds."""
+    P, Q, J, H, S = int(page_len.numel()), int(pat_len.numel()), int(jobs.numel()) // 2, int(max_hits), int(sigma)
+    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
+                                  ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('opt', opt, torch.int64, Q), ('pat_len', pat_len, torch.int32, Q),
+                                  ('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J), ('scratch', scratch, torch.uint8, 0)):
+        if t is None:
+            raise ValueError('%s is missing' % name)
+        _c(t, name)
+        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if jobs.numel() != 2 * J:
+        raise ValueError('jobs must hold (page, pattern) pairs, got %d integers' % jobs.numel())
+    outs = []
+    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
+        if t is None:
+            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
+        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
+        outs.append(t)
+    rc = _lib.lib().omp_page_pattern_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(masks), ptr(opt), ptr(pat_len), ptr(k), Q,
+                                            ptr(jobs), J, S, H, ptr(scratch), int(scratch.numel()), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
+    _lib.check(rc, 'omp_page_pattern_search')
+    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+
+
 def _reading_tables(polys, tables, host_tables, n_groups):
     N, G = int(polys.shape[0]), int(n_groups)
     for name, tt, numel in (('polys', polys, 32 * N), ('tables', tables, 3 * G + 1)):

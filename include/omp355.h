@@ -829,6 +829,36 @@ int omp_page_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page
                     int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best, int32_t* n_hits,
                     int32_t* hits, omp_stream_t s);
 
+/* ---- page patterns: dates, amounts and ids in the text of read pages ----
+ * A pattern is 1 .. 64 positions, each a character class, each mandatory or optional; insert / delete / substitute cost 1, skipping
+ * an optional position is free: D[0][j] = 0, D[i][0] = D[i-1][0] + skip_i, D[i][j] = min(D[i-1][j-1] + (t_j not in C_i),
+ * D[i-1][j] + skip_i, D[i][j-1] + 1), skip_i = 0 for an optional position and 1 otherwise; v_j = min(D[P][j], k + 1).
+ * utils/page_pattern.py holds the specification (row_py, search_cpu); this entry point equals it on every integer.
+ *   pool, pool_bytes   uint8 character codes 0 .. sigma - 1; a code at or above sigma is in no class
+ *   page_off, page_len int32 [n_pages]: page p is pool[page_off, page_off + page_len), 0 .. 65535 characters
+ *   masks              uint64 [n_patterns][sigma + 1], 8-byte aligned: bit i of masks[q][c] says that code c is in the class of position
+ *                      i of pattern q; row sigma is not read (it counts as 0)
+ *   opt, pat_len, k    uint64 / int32 / int32 [n_patterns]: bit i of opt says that position i is optional; P = pat_len in 1 .. 64, no opt
+ *                      bit at or above P, Mand = P - popcount(opt) >= 1, and the tolerance 0 <= k <= min(Mand - 1, 8)
+ *   jobs               int32 [n_jobs, 2]: (page, pattern); 1 .. 2^20 jobs
+ *   max_hits           H, 1 .. 64
+ *   scratch            8-byte aligned, at least n_jobs * 64 * max_hits * 8 bytes (per lane the first H hits of its chunk of the text)
+ *   best               int32 [n_jobs, 2] = (dist, end): the least v_j and the least j that attains it; (k + 1, 0) when nothing is within k
+ *   n_hits             int32 [n_jobs]: the ends j in 1 .. n with v_j <= k, v_j <= v_{j-1} and (j == n or v_j < v_{j+1})
+ *   hits               int32 [n_jobs, H, 3] = (end, dist, start) of the first min(n_hits, H) hits in ascending end, the rest -1;
+ *                      start is the LEAST s >= end - (P + dist) whose anchored cost against text[s, end) equals dist (the longest match;
+ *                      omp_page_search reports the shortest)
+ * OMP_ERR_INVALID, nothing launched: a null pointer, n_jobs outside 1 .. 2^20, no pages, no patterns, sigma outside 0 .. 254, max_hits
+ *   outside 1 .. 64, too little scratch, scratch, masks or opt not 8-byte aligned.  The tables live in device memory, so what only they
+ *   show is REFUSED on the device: a job whose page or pattern is not there, whose P is outside 1 .. 64, whose opt word holds a bit at
+ *   or above P or leaves no mandatory position, whose k is outside 0 .. min(Mand - 1, 8), whose page is above 65535 characters or lies
+ *   outside the pool gets n_hits = -1 (best and hits -1) and reads nothing of the pool.
+ * One launch, one wave per job; no allocation, no synchronisation, no atomics: the hits do not depend on scheduling. */
+int omp_page_pattern_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page_off, const int32_t* page_len, int n_pages,
+                            const uint64_t* masks, const uint64_t* opt, const int32_t* pat_len, const int32_t* k, int n_patterns,
+                            const int32_t* jobs, int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best,
+                            int32_t* n_hits, int32_t* hits, omp_stream_t s);
+
 /* ---- page text alignment: the optimal edit script of whole pages ----
  * The script behind omp_page_edit_distance's number: a is the prediction (rows i), b the ground truth (columns j), D the Levenshtein
  * table with D[i][0] = i and D[0][j] = j.  The walk runs from (la, lb) to (0, 0) and takes the FIRST rule that applies:
