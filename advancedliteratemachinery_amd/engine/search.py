@@ -1,5 +1,6 @@
 """Page search on records: where a phrase (find_text: DESIGN.md section 25, utils/page_search.py, csrc/page_search.hip) or a shape such as a
-date, an amount or an id (find_pattern: DESIGN.md section 29, utils/page_pattern.py, csrc/page_pattern.hip) stands on a read page, which
+date, an amount or an id (find_pattern: DESIGN.md section 29, utils/page_pattern.py, csrc/page_pattern.hip; find_regex: the same with
+groups, alternation and real loops, exactly: DESIGN.md section 30, utils/page_regex.py, csrc/page_regex.hip) stands on a read page, which
 words carry it and how badly it was misread."""
 import numpy as np
 
@@ -145,4 +146,58 @@ def find_pattern(records, patterns, field='rec', max_dist=None, max_ratio=0.0, s
         hits, dropped = _carried(records[b], text, w_start, w_start + w_len, res['hits'][at])
         out[b].append(dict(pattern=src, name=name, P=parsed[q].P, k=k[q], best=None if end == 0 else dist, n_hits=int(res['n_hits'][at]), dropped=dropped,
                            hits=hits))
+    return out
+
+
+def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_hits=16, searcher=None, device=None):
+    """records: as find_text takes them, IN THE ORDER TO BE READ.  expressions: a list for all images, or one list (not tuple) per image;
+    an expression is a string in the syntax of utils.page_regex.parse_regex (find_pattern's atoms with groups, `|` at any depth and the
+    quantifiers ? * + {n} {a,b} {a,}; `*`, `+` and `{a,}` are real loops) or a (name, string) tuple.  Every image becomes one text
+    (page_index); `normalise` is applied to the page words ONLY, never to an expression.  An expression is matched exactly: there is no
+    tolerance.
+    searcher: a utils.page_regex.RegexSearcher, or anything with its `run` (HostRegexSearcher: the specification); default: one on
+    `device` (default 'cuda').  All images and expressions go through ONE searcher.run.
+    -> per image a list with one dict per expression: pattern (the string), name (None for a bare string), P (its positions), best (0
+    when the expression stands somewhere on the page, else None), n_hits, dropped, hits.  A hit is find_pattern's dict (dist = 0, chars,
+    text, words, records, box): it ends at the LAST column of a run of consecutive ends and starts at the LEAST start, the longest match
+    (`\\d+` in `12345 ` is `12345`).  An expression in find_pattern's subset gets the hits find_pattern gives it at k = 0.  A hit that touches
+    no word is dropped and counted."""
+    from ..utils import page_regex as PR
+    from ..utils.page_search import page_index
+    records = [list(recs) for recs in records]
+    for b, recs in enumerate(records):
+        for r in recs:
+            if not isinstance(r, dict) or 'polys' not in r:
+                raise ValueError('image %d: find_regex needs text-spotting records (dicts with `polys`)' % b)
+    expressions = list(expressions)
+    if expressions and all(isinstance(p, list) for p in expressions):      # a tuple is a (name, string) pair, so per-image lists are LISTS
+        if len(expressions) != len(records):
+            raise ValueError('expressions holds %d lists for %d images' % (len(expressions), len(records)))
+        lists = [list(p) for p in expressions]
+    else:
+        lists = [expressions] * len(records)
+    pages = [page_index(recs, field, sep, normalise) for recs in records]
+    table, parsed, jobs, named = {}, [], [], []
+    for b, ps in enumerate(lists):
+        for p in ps:
+            name, src = (None, p) if isinstance(p, str) else p if isinstance(p, tuple) and len(p) == 2 else (None, None)
+            if not isinstance(src, str) or not (name is None or isinstance(name, str)):
+                raise ValueError('an expression is a string or a (name, string) pair, got %r' % (p,))
+            if src not in table:
+                table[src] = len(table)
+                parsed.append(PR.parse_regex(src))
+            jobs.append((b, table[src]))
+            named.append((name, src))
+    out = [[] for _ in records]
+    if not jobs:
+        return out
+    pool, page_off, page_len, masks, first, last, follow, pred, pat_len, _ = PR.encode_regex([p[0] for p in pages], parsed)
+    if searcher is None:
+        searcher = PR.RegexSearcher('cuda' if device is None else device)
+    res = searcher.run(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, np.asarray(jobs, dtype=np.int32), int(max_hits))
+    for at, ((b, q), (name, src)) in enumerate(zip(jobs, named)):
+        text, w_start, w_len = pages[b]
+        dist, end = (int(v) for v in res['best'][at])
+        hits, dropped = _carried(records[b], text, w_start, w_start + w_len, res['hits'][at])
+        out[b].append(dict(pattern=src, name=name, P=parsed[q].P, best=None if end == 0 else dist, n_hits=int(res['n_hits'][at]), dropped=dropped, hits=hits))
     return out

@@ -191,16 +191,17 @@ def tolerance(mand, max_dist=None, max_ratio=0.0):
 # ---------------------------------------------------------------------------------------------
 # codes
 # ---------------------------------------------------------------------------------------------
-def encode_patterns(page_texts, patterns):
-    """page texts and Q patterns (Pattern objects, or strings parsed without rep_max) -> (pool uint8, page_off, page_len int32 [pages],
-    masks uint64 [Q, sigma + 1], opt uint64 [Q], pat_len int32 [Q], sigma).  Equal page texts share one pool range."""
-    page_texts, patterns = list(page_texts), [parse_pattern(p) for p in patterns]
+def encode_classes(page_texts, atom_rows):
+    """what encode_patterns and page_regex.encode_regex share: page texts and, per pattern, the re sources of its positions -> (pool uint8,
+    page_off, page_len int32 [pages], masks uint64 [Q, sigma + 1], sigma).  A page character's signature is the tuple of its memberships in
+    every distinct atom of the call; signatures get the dense codes in order of first appearance.  Equal page texts share one pool range."""
+    page_texts, atom_rows = list(page_texts), [tuple(r) for r in atom_rows]
     for t in page_texts:
         if len(t) > LEN_MAX:
             raise ValueError('a page text holds %d characters; the limit is %d' % (len(t), LEN_MAX))
     atoms = {}
-    for p in patterns:
-        for a in p.atoms:
+    for row in atom_rows:
+        for a in row:
             if a not in atoms:
                 atoms[a] = (len(atoms), _compiled(a))
     tests = [rx for _, rx in atoms.values()]
@@ -225,13 +226,21 @@ def encode_patterns(page_texts, patterns):
     member = np.zeros((sigma + 1, max(len(atoms), 1)), dtype=bool)                # [code, atom]; row sigma: in no class
     for sig, c in sigs.items():
         member[c, :len(sig)] = sig
-    masks = np.zeros((len(patterns), sigma + 1), dtype=np.uint64)
-    for q, p in enumerate(patterns):
-        for i, a in enumerate(p.atoms):
+    masks = np.zeros((len(atom_rows), sigma + 1), dtype=np.uint64)
+    for q, row in enumerate(atom_rows):
+        for i, a in enumerate(row):
             masks[q] |= member[:, atoms[a][0]].astype(np.uint64) << np.uint64(i)
     i32 = lambda v: np.asarray(v, dtype=np.int32).reshape(-1)                   # noqa: E731
-    return (np.concatenate(chunks + [np.zeros(0, np.uint8)]).astype(np.uint8), i32(off), i32([len(t) for t in page_texts]), masks,
-            np.asarray([p.opt for p in patterns], dtype=np.uint64).reshape(-1), i32([p.P for p in patterns]), sigma)
+    return np.concatenate(chunks + [np.zeros(0, np.uint8)]).astype(np.uint8), i32(off), i32([len(t) for t in page_texts]), masks, sigma
+
+
+def encode_patterns(page_texts, patterns):
+    """page texts and Q patterns (Pattern objects, or strings parsed without rep_max) -> (pool uint8, page_off, page_len int32 [pages],
+    masks uint64 [Q, sigma + 1], opt uint64 [Q], pat_len int32 [Q], sigma).  Equal page texts share one pool range."""
+    patterns = [parse_pattern(p) for p in patterns]
+    pool, page_off, page_len, masks, sigma = encode_classes(page_texts, [p.atoms for p in patterns])
+    return (pool, page_off, page_len, masks, np.asarray([p.opt for p in patterns], dtype=np.uint64).reshape(-1),
+            np.asarray([p.P for p in patterns], dtype=np.int32).reshape(-1), sigma)
 
 
 # ---------------------------------------------------------------------------------------------

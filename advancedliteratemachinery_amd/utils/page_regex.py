@@ -1,0 +1,551 @@
+"""Page expressions: alternation, groups and unbounded repeats in the text of read pages.
+
+utils/page_pattern.py finds a flat row of character classes with up to k errors; this module finds a regular EXPRESSION over the same
+atoms, exactly (k = 0): groups, `|` at any depth and real loops.  A job is one (page, expression) pair.  The numpy / Python functions here
+are the DEFINITION; csrc/page_regex.hip (omp_page_regex_search) equals search_cpu on every integer.
+
+Syntax      parse_regex(): the atoms of parse_pattern (a literal, an escaped literal, `.`, \\d \\D \\w \\W \\s \\S, [...] / [^...]); groups
+            ( ) and (?: ), both non-capturing; `|` at any depth; the quantifiers ? * + {n} {a,b} {a,} on an atom or a group.  * + and {a,}
+            are real loops.  x{a,b} copies the positions of x: a mandatory copies and b - a optional ones; x{a,} is a copies with the loop
+            on the last one (x* for a = 0).  Anchors, \\b \\B \\A \\Z, back-references, lazy and possessive quantifiers, a quantifier on a
+            quantifier, empty groups or branches, any other (?...) extension, more than 64 positions after expansion and an expression
+            that matches the empty string are refused.  Whether a character is in an atom is decided by Python's re
+            (re.compile(atom, re.DOTALL).fullmatch(ch)).
+Automaton   Glushkov's position automaton: one state per position 0 .. P - 1, P <= 64, no epsilon moves.  first / last: the positions a
+            match can begin / end with; follow[i]: the positions that can come after position i; pred is follow transposed.  Bit i of
+            the state word D says that a match prefix has just consumed a character at position i.
+Codes       encode_regex(): the signature coding of page_pattern.encode_patterns (sigma <= 254, row sigma of a mask is 0).
+Step        D_0 = 0, D_j = (Follow(D_{j-1}) | first) & B(t_j), Follow(D) = OR of follow[i] over the bits i of D, B(c) = mask[c].
+            Column j (1-based) is an END iff D_j & last != 0.
+A hit       page_search's rule on v_j = 0 at an end, else 1, v_0 = 1, k = 0: the LAST column of a run of consecutive ends.  `\\d+` on
+            `12345 ` is one hit at 5.
+best        (0, the least end), or (1, 0) when there is no end.
+hits        int32 [J, H, 3] = (end, 0, start) in ascending end, -1 beyond the hits; n_hits counts all hits.
+start       the LEAST s with t[s:end] in the language (the longest match, find_pattern's convention), by the reverse walk
+            R = last & B(t_end); while R != 0: if R & first remember s; R = Pred(R) & B(t_{s-1}).  There is no span cap.
+Split       ends_chunked(): the kernel's way over a page.  The step is linear over union, so a lane runs its chunk from D = 0 (the
+            speculative pass), then takes the exit state of the lane before it and runs the bits it has not carried yet through its
+            chunk WITHOUT injecting first, until no lane gets a new bit.
+Limits      a page 0 .. 65535 characters, 1 .. 2^20 jobs a call, 1 .. 64 hits kept per job.
+"""
+import re
+from collections import namedtuple
+
+import numpy as np
+
+from .page_pattern import _ANCHOR_ESCAPES, _CLASS_ESCAPES, _compiled, encode_classes
+from .page_search import HITS_MAX, JOBS_MAX, hit_ends
+from .page_text import LEN_MAX, SIGMA_MAX, _DeviceStage
+
+POS_MAX = 64                    # positions an expression (csrc/page_regex.hip: PR_POS_MAX): one 64-bit state word
+CHUNK = 128                     # text columns per lane (csrc/page_regex.hip: PR_CHUNK)
+LANES = 64
+ROUND = CHUNK * LANES           # text columns per round of the wave
+_FULL = (1 << 64) - 1
+
+
+# ---------------------------------------------------------------------------------------------
+# syntax
+# ---------------------------------------------------------------------------------------------
+class Regex(object):
+    """a parsed expression: src, atoms (one re source per position), P, first, last (the bit words), follow and pred (uint64 [64], rows
+    at or above P zero; pred is follow transposed)"""
+
+    def __init__(self, src, atoms, first, last, follow):
+        self.src, self.atoms = src, tuple(atoms)
+        self.P = len(self.atoms)
+        self.first, self.last = int(first), int(last)
+        rows = [int(f) for f in follow] + [0] * (POS_MAX - len(follow))
+        self.follow = np.asarray(rows, dtype=np.uint64)
+        self.pred = np.asarray(_transpose(rows), dtype=np.uint64)
+
+    def __repr__(self):
+        return 'Regex(%r, P=%d)' % (self.src, self.P)
+
+
+def _transpose(rows):
+    out = [0] * POS_MAX
+    for i, f in enumerate(rows):
+        f = int(f)
+        while f:
+            j = (f & -f).bit_length() - 1
+            out[j] |= 1 << i
+            f &= f - 1
+    return out
+
+
+def _bits(x):
+    x = int(x)
+    while x:
+        yield (x & -x).bit_length() - 1
+        x &= x - 1
+
+
+_BRACE = re.compile(r'\{(\d*)(,?)(\d*)\}')
+
+
+class _Parser(object):
+    """recursive descent: alt := seq ('|' seq)*; seq := item+; item := (atom | group) quantifier?.  A node is ('atom', source),
+    ('cat', [nodes]), ('alt', [nodes]), ('opt', node), ('star', node) or ('plus', node); a counted repeat lists the same node several times,
+    and the positions are numbered when the automaton is built, so every listing gets positions of its own."""
+
+    def __init__(self, src):
+        self.src, self.n, self.i = src, len(src), 0
+
+    def bad(self, at, what):
+        return ValueError('expression %r, offset %d: %s' % (self.src, at, what))
+
+    def alt(self, depth):
+        at = self.i
+        branches = [self.seq(depth)]
+        while self.i < self.n and self.src[self.i] == '|':
+            self.i += 1
+            branches.append(self.seq(depth))
+            if sum(b[1] for b in branches) > POS_MAX:
+                raise self.bad(at, 'the expression holds more than %d positions after expansion' % POS_MAX)
+        return branches[0] if len(branches) == 1 else (('alt', [b[0] for b in branches]), sum(b[1] for b in branches))
+
+    def seq(self, depth):
+        src, n, at = self.src, self.n, self.i
+        items, size = [], 0
+        while self.i < n and src[self.i] != '|' and not (src[self.i] == ')' and depth):
+            node, s = self.item(depth)
+            items.append(node)
+            size += s
+            if size > POS_MAX:
+                raise self.bad(at, 'the expression holds more than %d positions after expansion' % POS_MAX)
+        if not items:
+            raise self.bad(at, 'an empty group or branch')
+        return (items[0] if len(items) == 1 else ('cat', items)), size
+
+    def atom(self, depth):
+        src, n, at = self.src, self.n, self.i
+        ch = src[at]
+        if ch == '\\':
+            if at + 1 >= n:
+                raise self.bad(at, 'a backslash at the end')
+            e = src[at + 1]
+            if e.isdigit():
+                raise self.bad(at, 'back-references are not supported')
+            if e in _ANCHOR_ESCAPES:
+                raise self.bad(at, 'anchors and word boundaries are not supported')
+            atom = src[at:at + 2]
+            if e not in _CLASS_ESCAPES:                                          # an escaped literal, \n, \t, ...: re says which exist
+                try:
+                    _compiled(atom)
+                except (re.error, Warning):
+                    raise self.bad(at, 'the escape %r is not supported' % atom)
+            self.i = at + 2
+            return ('atom', atom), 1
+        if ch == '[':
+            j = at + 1
+            if j < n and src[j] == '^':
+                j += 1
+            if j < n and src[j] == ']':
+                j += 1
+            while j < n and src[j] != ']':
+                j += 2 if src[j] == '\\' else 1
+            if j >= n:
+                raise self.bad(at, 'a character class that is not closed')
+            atom = src[at:j + 1]
+            try:
+                _compiled(atom)
+            except (re.error, Warning) as e:
+                raise self.bad(at, 'the character class %r is refused by re: %s' % (atom, e))
+            self.i = j + 1
+            return ('atom', atom), 1
+        if ch == '(':
+            self.i = at + 1
+            if src.startswith('(?', at):
+                if not src.startswith('(?:', at):
+                    raise self.bad(at, 'the extension %r is not supported; only (?: ) is' % src[at:at + 3])
+                self.i = at + 3
+            node = self.alt(depth + 1)
+            if self.i >= n or src[self.i] != ')':
+                raise self.bad(at, 'a group that is not closed')
+            self.i += 1
+            return node
+        if ch == ')':
+            raise self.bad(at, 'a parenthesis that closes nothing (write \\))')
+        if ch in '^$':
+            raise self.bad(at, 'anchors are not supported')
+        if ch in '*+?{':
+            raise self.bad(at, 'a quantifier with nothing to repeat')
+        if ch == '}':
+            raise self.bad(at, 'a brace that closes nothing (write \\})')
+        self.i = at + 1
+        return ('atom', '\\' + ch if ch in ']' else ch), 1
+
+    def item(self, depth):
+        src, n, at = self.src, self.n, self.i
+        node, size = self.atom(depth)
+        i = self.i
+        if i >= n or src[i] not in '*+?{':
+            return node, size
+        qat, q = i, src[i]
+        if q == '?':
+            lo, hi, i = 0, 1, i + 1
+        elif q == '*':
+            lo, hi, i = 0, None, i + 1
+        elif q == '+':
+            lo, hi, i = 1, None, i + 1
+        else:
+            m = _BRACE.match(src, i)
+            if m is None or (m.group(1) == '' and m.group(3) == ''):
+                raise self.bad(qat, 'a brace that is no {n}, {a,b} or {a,} quantifier (write \\{)')
+            a, comma, b = m.groups()
+            lo = int(a) if a else 0
+            hi = lo if not comma else int(b) if b else None
+            if hi is not None and hi < lo:
+                raise self.bad(qat, 'a quantifier {a,b} with b < a')
+            if hi == 0:
+                raise self.bad(qat, 'a quantifier that repeats nothing')
+            i = m.end()
+        if i < n and src[i] in '?+':
+            raise self.bad(i, 'lazy and possessive quantifiers are not supported')
+        if i < n and src[i] in '*{':
+            raise self.bad(i, 'a quantifier on a quantifier')
+        self.i = i
+        copies = max(lo, 1) if hi is None else hi
+        if copies * size > POS_MAX:
+            raise self.bad(at, 'the expression holds more than %d positions after expansion' % POS_MAX)
+        if hi is None:                                                           # x{a,}: a copies, the loop on the last one; x* for a = 0
+            parts = [node] * (lo - 1) + [('plus', node)] if lo else [('star', node)]
+        else:
+            parts = [node] * lo + [('opt', node)] * (hi - lo)
+        return (parts[0] if len(parts) == 1 else ('cat', parts)), copies * size
+
+
+def _glushkov(node, atoms, follow):
+    """number the positions of `node` after those in `atoms`, fill their follow words -> (nullable, first, last)"""
+    kind, arg = node
+    if kind == 'atom':
+        atoms.append(arg)
+        follow.append(0)
+        return False, 1 << (len(atoms) - 1), 1 << (len(atoms) - 1)
+    if kind == 'cat':
+        null, first, last = True, 0, 0
+        for child in arg:
+            n, f, l = _glushkov(child, atoms, follow)
+            for i in _bits(last):
+                follow[i] |= f
+            first |= f if null else 0
+            last = l | (last if n else 0)
+            null = null and n
+        return null, first, last
+    if kind == 'alt':
+        parts = [_glushkov(child, atoms, follow) for child in arg]
+        return any(p[0] for p in parts), sum(p[1] for p in parts), sum(p[2] for p in parts)
+    n, f, l = _glushkov(arg, atoms, follow)
+    if kind in ('star', 'plus'):
+        for i in _bits(l):
+            follow[i] |= f
+    return (n if kind == 'plus' else True), f, l
+
+
+def parse_regex(src):
+    """an expression as the caller wrote it -> Regex.  Every refusal is a ValueError that names the expression and the offset."""
+    if isinstance(src, Regex):
+        return src
+    if not isinstance(src, str):
+        raise ValueError('an expression must be a string, got %r' % (src,))
+    p = _Parser(src)
+    if not src:
+        raise p.bad(0, 'the expression holds no position')
+    node, size = p.alt(0)
+    assert p.i == p.n and size <= POS_MAX
+    atoms, follow = [], []
+    null, first, last = _glushkov(node, atoms, follow)
+    if null:
+        raise p.bad(0, 'the expression matches the empty string')
+    return Regex(src, atoms, first, last, follow)
+
+
+# ---------------------------------------------------------------------------------------------
+# codes
+# ---------------------------------------------------------------------------------------------
+def encode_regex(page_texts, regexes):
+    """page texts and Q expressions (Regex objects or strings) -> (pool uint8, page_off, page_len int32 [pages], masks uint64
+    [Q, sigma + 1], first, last uint64 [Q], follow, pred uint64 [Q, 64], pat_len int32 [Q], sigma).  The coding is encode_patterns'."""
+    regexes = [parse_regex(r) for r in regexes]
+    pool, page_off, page_len, masks, sigma = encode_classes(page_texts, [r.atoms for r in regexes])
+    u64 = lambda v: np.asarray(v, dtype=np.uint64)                              # noqa: E731
+    return (pool, page_off, page_len, masks, u64([r.first for r in regexes]).reshape(-1), u64([r.last for r in regexes]).reshape(-1),
+            u64([r.follow for r in regexes]).reshape(-1, POS_MAX), u64([r.pred for r in regexes]).reshape(-1, POS_MAX),
+            np.asarray([r.P for r in regexes], dtype=np.int32).reshape(-1), sigma)
+
+
+# ---------------------------------------------------------------------------------------------
+# the specification
+# ---------------------------------------------------------------------------------------------
+Tables = namedtuple('Tables', 'mask first last follow pred P')
+
+
+def tables(masks, first, last, follow, pred, pat_len, q=0):
+    """expression q of encode_regex's outputs, checked -> Tables(mask uint64 [sigma + 1], first, last, follow [64], pred [64], P) with
+    Python integers"""
+    mask = np.asarray(masks, dtype=np.uint64)[q].reshape(-1)
+    P = int(np.asarray(pat_len).reshape(-1)[q])
+    fi, la = int(np.asarray(first).reshape(-1)[q]), int(np.asarray(last).reshape(-1)[q])
+    fo = [int(v) for v in np.asarray(follow, dtype=np.uint64).reshape(-1, POS_MAX)[q]]
+    pr = [int(v) for v in np.asarray(pred, dtype=np.uint64).reshape(-1, POS_MAX)[q]]
+    if not 1 <= P <= POS_MAX:
+        raise ValueError('an expression takes 1 .. %d positions, got %d' % (POS_MAX, P))
+    if mask.size < 1:
+        raise ValueError('a mask table holds sigma + 1 >= 1 words')
+    if any(w >> P for w in [fi, la] + fo + pr) or any(fo[P:]) or any(pr[P:]):
+        raise ValueError('first, last, follow or pred hold bits or rows at or above P = %d' % P)
+    if fi == 0 or la == 0:
+        raise ValueError('first or last is empty: the expression matches nothing')
+    return Tables(mask, fi, la, fo, pr, P)
+
+
+def _classes(mask, t):
+    """the class word of every text character, as Python integers: codes at or above sigma read row sigma"""
+    t = np.asarray(t, dtype=np.uint8).reshape(-1)
+    if t.size > LEN_MAX:
+        raise ValueError('a text holds %d codes; the limit is %d' % (t.size, LEN_MAX))
+    return mask[np.minimum(t.astype(np.int64), mask.size - 1)].tolist()
+
+
+def _byte_tables(rows, P):
+    """T[b][v] = OR of rows[8 b + i] over the bits i of v, for b < ceil(P / 8): Follow (or Pred) of a state word by one lookup per byte"""
+    out = []
+    for b in range((P + 7) // 8):
+        T = [0] * 256
+        for v in range(1, 256):
+            low = v & -v
+            T[v] = T[v ^ low] | rows[8 * b + low.bit_length() - 1]
+        out.append(T)
+    return out
+
+
+def _move(T, D):
+    F, b = 0, 0
+    while D:
+        F |= T[b][D & 255]
+        D >>= 8
+        b += 1
+    return F
+
+
+def ends_py(tab, t):
+    """the end columns of text t, ascending, int32: sets of positions, no bit tricks -- the ground truth of the step"""
+    B = [frozenset(_bits(b)) for b in _classes(tab.mask, t)]
+    first, last = frozenset(_bits(tab.first)), frozenset(_bits(tab.last))
+    follow = [frozenset(_bits(f)) for f in tab.follow]
+    D, out = frozenset(), []
+    for j, b in enumerate(B, 1):
+        reach = set(first)
+        for i in D:
+            reach |= follow[i]
+        D = frozenset(reach) & b
+        if D & last:
+            out.append(j)
+    return np.asarray(out, dtype=np.int32)
+
+
+def _end_flags(tab, t):
+    """bool [n + 1]: column j is an end (column 0 never is)"""
+    B = _classes(tab.mask, t)
+    T, first, last = _byte_tables(tab.follow, tab.P), tab.first, tab.last
+    flags = np.zeros(len(B) + 1, dtype=bool)
+    D = 0
+    for j, b in enumerate(B, 1):
+        D = (_move(T, D) | first) & b
+        if D & last:
+            flags[j] = True
+    return flags
+
+
+def ends_cpu(tab, t):
+    """the end columns of text t, ascending, int32, by the words: D_j = (Follow(D_{j-1}) | first) & B(t_j); j is an end iff D_j & last"""
+    return np.flatnonzero(_end_flags(tab, t)).astype(np.int32)
+
+
+def match_start(tab, t, end):
+    """the least s with t[s:end] in the language, by the reverse walk; `end` must be an end column"""
+    end = int(end)
+    B = _classes(tab.mask, np.asarray(t, dtype=np.uint8).reshape(-1)[:end])
+    T = _byte_tables(tab.pred, tab.P)
+    s, found = end - 1, None
+    R = tab.last & B[s]
+    while R:
+        if R & tab.first:
+            found = s
+        if s == 0:
+            break
+        s -= 1
+        R = _move(T, R) & B[s]
+    if found is None:
+        raise AssertionError('column %d is no end: the reverse walk found no start' % end)
+    return found
+
+
+def ends_chunked(tab, t, chunk=CHUNK, lanes=LANES):
+    """ends_cpu by the split the kernel runs, with `lanes` lanes of `chunk` columns a round of the wave.  Per round: lane l runs its chunk
+    from D = 0 (lane 0: from the exact exit state of the round before) with first injected at every column, and keeps its end bits and
+    its exit state X.  Then, until no lane gets a new bit: every lane l >= 1 that holds text takes X of lane l - 1, keeps the bits it
+    has not carried yet, runs them through its chunk WITHOUT injection (C = Follow(C) & B), ORs C & last into its end bits and C after
+    its last column into X, and leaves the chunk as soon as C == 0.  -> (ends int32 ascending, the carry rounds of every wave round)"""
+    chunk, lanes = int(chunk), int(lanes)
+    B = _classes(tab.mask, t)
+    n = len(B)
+    T, first, last = _byte_tables(tab.follow, tab.P), tab.first, tab.last
+    flags = np.zeros(n + 1, dtype=bool)
+    carry_in, rounds = 0, []
+    for r0 in range(0, n, chunk * lanes):
+        lo = [min(r0 + l * chunk, n) for l in range(lanes + 1)]                   # lane l owns the characters lo[l] .. lo[l + 1] - 1
+        X = [0] * lanes
+        for l in range(lanes):
+            D = carry_in if l == 0 else 0
+            for c in range(lo[l], lo[l + 1]):
+                D = (_move(T, D) | first) & B[c]
+                if D & last:
+                    flags[c + 1] = True
+            X[l] = D
+        carried, count = [0] * lanes, 0
+        while True:
+            new = [0] + [X[l - 1] & ~carried[l] if lo[l + 1] > lo[l] else 0 for l in range(1, lanes)]     # all lanes read before any writes
+            if not any(new):
+                break
+            count += 1
+            for l in range(1, lanes):
+                C = new[l]
+                carried[l] |= C
+                for c in range(lo[l], lo[l + 1]):
+                    if not C:
+                        break
+                    C = _move(T, C) & B[c]
+                    if C & last:
+                        flags[c + 1] = True
+                X[l] |= C
+        rounds.append(count)
+        carry_in = X[lanes - 1]
+    return np.flatnonzero(flags).astype(np.int32), rounds
+
+
+def _check_search(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits):
+    pool = np.ascontiguousarray(pool, dtype=np.uint8).reshape(-1)
+    po, pl, P = [np.asarray(t, dtype=np.int64).reshape(-1) for t in (page_off, page_len, pat_len)]
+    first, last = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1) for t in (first, last)]
+    masks = np.ascontiguousarray(masks, dtype=np.uint64)
+    follow, pred = [np.ascontiguousarray(t, dtype=np.uint64) for t in (follow, pred)]
+    jobs = np.asarray(jobs, dtype=np.int64).reshape(-1, 2)
+    if po.size != pl.size:
+        raise ValueError('page_off and page_len hold one entry per page, got %d and %d' % (po.size, pl.size))
+    Q = P.size
+    if masks.ndim != 2 or masks.shape[1] < 1 or masks.shape[1] > SIGMA_MAX + 1 or not (masks.shape[0] == first.size == last.size == Q):
+        raise ValueError('masks [Q, sigma + 1], first, last and pat_len hold one entry per expression, got %s, %d, %d and %d'
+                         % (masks.shape, first.size, last.size, Q))
+    if follow.shape != (Q, POS_MAX) or pred.shape != (Q, POS_MAX):
+        raise ValueError('follow and pred are [Q, %d], got %s and %s' % (POS_MAX, follow.shape, pred.shape))
+    max_hits = int(max_hits)
+    if not 1 <= max_hits <= HITS_MAX:
+        raise ValueError('max_hits must be 1 .. %d, got %d' % (HITS_MAX, max_hits))
+    if jobs.shape[0] > JOBS_MAX:
+        raise ValueError('a call takes %d jobs, got %d' % (JOBS_MAX, jobs.shape[0]))
+    if pl.size and ((pl < 0).any() or (pl > LEN_MAX).any()):
+        raise ValueError('a page length is outside 0 .. %d' % LEN_MAX)
+    if po.size and ((po < 0).any() or (po + pl > pool.size).any()):
+        raise ValueError('a range lies outside the pool of %d codes' % pool.size)
+    if Q and ((P < 1).any() or (P > POS_MAX).any()):
+        raise ValueError('an expression length is outside 1 .. %d' % POS_MAX)
+    if Q:
+        below = np.where(P >= POS_MAX, np.uint64(_FULL), (np.uint64(1) << np.minimum(P, POS_MAX - 1).astype(np.uint64)) - np.uint64(1))   # the bits below P
+        rows = np.arange(POS_MAX)[None, :] < P[:, None]                                                  # the rows below P
+        allowed = np.where(rows, below[:, None], np.uint64(0))
+        if ((first | last) & ~below).any() or ((follow | pred) & ~allowed).any():
+            raise ValueError('first, last, follow or pred hold bits or rows at or above P')
+        if (first == 0).any() or (last == 0).any():
+            raise ValueError('first or last of an expression is empty')
+        bits = lambda w: np.unpackbits(w.view(np.uint8).reshape(Q, POS_MAX, 8), axis=2, bitorder='little')  # noqa: E731  [q, row, bit]
+        if (bits(follow) != bits(pred).transpose(0, 2, 1)).any():
+            raise ValueError('pred is not follow transposed')
+    if jobs.size and ((jobs < 0).any() or (jobs[:, 0] >= pl.size).any() or (jobs[:, 1] >= Q).any()):
+        raise ValueError('a job names a page or an expression that is not there')
+    return [pool, po.astype(np.int32), pl.astype(np.int32), masks, first, last, follow, pred, P.astype(np.int32),
+            np.ascontiguousarray(jobs.astype(np.int32)), max_hits]
+
+
+def search_cpu(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits):
+    """the definition, for the flat inputs omp_page_regex_search takes -> dict(best int32 [J, 2] = (0, the least end) or (1, 0),
+    n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, 0, start), -1 where there is no hit)"""
+    pool, po, pl, masks, first, last, follow, pred, P, jobs, H = _check_search(pool, page_off, page_len, masks, first, last, follow, pred,
+                                                                               pat_len, jobs, max_hits)
+    J = jobs.shape[0]
+    best = np.zeros((J, 2), dtype=np.int32)
+    n_hits = np.zeros(J, dtype=np.int32)
+    hits = np.full((J, H, 3), -1, dtype=np.int32)
+    done, tabs = {}, {}
+    for j, (p, q) in enumerate(jobs.tolist()):
+        key = (po[p], pl[p], q)
+        if key not in done:
+            if q not in tabs:
+                tabs[q] = tables(masks, first, last, follow, pred, P, q)
+            t = pool[po[p]:po[p] + pl[p]]
+            v = 1 - _end_flags(tabs[q], t).astype(np.int32)                    # v_0 = 1: column 0 is never an end
+            ends = hit_ends(v, 0)
+            least = np.flatnonzero(v == 0)
+            rows = [(int(e), 0, match_start(tabs[q], t, int(e))) for e in ends[:H].tolist()]
+            done[key] = ((0, int(least[0])) if least.size else (1, 0), int(ends.size), rows)
+        b, c, rows = done[key]
+        best[j] = b
+        n_hits[j] = c
+        if rows:
+            hits[j, :len(rows)] = rows
+    return dict(best=best, n_hits=n_hits, hits=hits)
+
+
+class HostRegexSearcher(object):
+    """RegexSearcher's `run` from the specification (search_cpu): what the device stage must equal"""
+
+    def __init__(self):
+        self.calls = 0
+
+    def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits):
+        self.calls += 1
+        return search_cpu(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits)
+
+
+# ---------------------------------------------------------------------------------------------
+# the device stage
+# ---------------------------------------------------------------------------------------------
+class RegexSearcher(_DeviceStage):
+    """search_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_regex_search launch per JOBS_MAX
+    jobs (the kernel needs no scratch), and ONE download of best, n_hits and hits.  There is no CPU fallback: HostRegexSearcher is the
+    specification."""
+    HOST = 'HostRegexSearcher'
+
+    def __init__(self, device):
+        super().__init__(device, 0)
+
+    def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits):
+        """the inputs of search_cpu -> the dict of search_cpu, as numpy.  sigma is masks.shape[1] - 1."""
+        import torch
+
+        from .. import ops
+        pool, po, pl, masks, first, last, follow, pred, P, jobs, H = _check_search(pool, page_off, page_len, masks, first, last, follow, pred,
+                                                                                   pat_len, jobs, max_hits)
+        sigma = masks.shape[1] - 1
+        J = jobs.shape[0]
+        self.calls += 1
+        parts = [(lo, min(lo + JOBS_MAX, J)) for lo in range(0, J, JOBS_MAX)]
+        self.chunks = len(parts)
+        if J == 0:
+            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
+        with torch.cuda.device(self.device):
+            # the 64-bit words travel as int64: the same bytes
+            i64 = lambda a: a.reshape(-1).view(np.int64)                        # noqa: E731
+            (d_masks, d_first, d_last, d_follow, d_pred, d_po, d_pl, d_P, d_jobs), d_pool = self._upload(
+                (i64(masks), i64(first), i64(last), i64(follow), i64(pred), po, pl, P, jobs.reshape(-1)), pool)
+            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
+            for lo, hi in parts:
+                ops.page_regex_search(d_pool, pool.size, d_po, d_pl, d_masks, d_first, d_last, d_follow, d_pred, d_P, d_jobs[2 * lo:2 * hi], sigma, H,
+                                      best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
+            host = out.cpu().numpy()                                          # the one download
+        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
+        if (res['n_hits'] < 0).any():
+            raise RuntimeError('omp_page_regex_search refused a job (a length above the limits, a range outside the pool, or first, last, follow '
+                               'or pred words with bits or rows at or above P)')
+        return res

@@ -859,6 +859,36 @@ int omp_page_pattern_search(const uint8_t* pool, int64_t pool_bytes, const int32
                             const int32_t* jobs, int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best,
                             int32_t* n_hits, int32_t* hits, omp_stream_t s);
 
+/* ---- page expressions: groups, alternation and real loops in the text of read pages ----
+ * An expression is Glushkov's position automaton of P = 1 .. 64 positions, each a character class: first / last are the positions a
+ * match can begin / end with, follow[i] the positions that can come after position i, pred is follow transposed.  Bit i of the state D
+ * says that a match prefix has just consumed a character at position i: D_0 = 0, D_j = (Follow(D_{j-1}) | first) & masks[t_j] with
+ * Follow(D) = OR of follow[i] over the bits i of D; column j (1-based) is an END iff D_j & last != 0.  The match is exact (no errors).
+ * utils/page_regex.py holds the specification (ends_cpu, search_cpu); this entry point equals it on every integer.
+ *   pool, pool_bytes   uint8 character codes 0 .. sigma - 1; a code at or above sigma is in no class
+ *   page_off, page_len int32 [n_pages]: page p is pool[page_off, page_off + page_len), 0 .. 65535 characters
+ *   masks              uint64 [n_expressions][sigma + 1], 8-byte aligned: bit i of masks[q][c] says that code c is in the class of
+ *                      position i of expression q; row sigma is not read (it counts as 0)
+ *   first, last        uint64 [n_expressions], neither 0, no bit at or above P
+ *   follow, pred       uint64 [n_expressions][64]: no bit at or above P, the rows at or above P zero
+ *   pat_len            int32 [n_expressions]: P in 1 .. 64
+ *   jobs               int32 [n_jobs, 2]: (page, expression); 1 .. 2^20 jobs
+ *   max_hits           H, 1 .. 64
+ *   best               int32 [n_jobs, 2]: (0, the least end), or (1, 0) when the page holds no end
+ *   n_hits             int32 [n_jobs]: the ends whose next column is no end (the LAST column of every run of consecutive ends)
+ *   hits               int32 [n_jobs, H, 3] = (end, 0, start) of the first min(n_hits, H) hits in ascending end, the rest -1; start is
+ *                      the LEAST s with text[s, end) in the language (the longest match), found by a walk back that has no span cap
+ * OMP_ERR_INVALID, nothing launched: a null pointer, n_jobs outside 1 .. 2^20, no pages, no expressions, sigma outside 0 .. 254, max_hits
+ *   outside 1 .. 64, masks, first, last, follow or pred not 8-byte aligned.  The tables live in device memory, so what only they show is
+ *   REFUSED on the device: a job whose page or expression is not there, whose P is outside 1 .. 64, whose first, last, follow or pred
+ *   words hold a bit or a row at or above P, whose first or last is 0, whose page is above 65535 characters or lies outside the pool
+ *   gets n_hits = -1 (best and hits -1) and reads nothing of the pool.
+ * One launch, one wave per job, no scratch; no allocation, no synchronisation, no atomics: the hits do not depend on scheduling. */
+int omp_page_regex_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page_off, const int32_t* page_len, int n_pages,
+                          const uint64_t* masks, const uint64_t* first, const uint64_t* last, const uint64_t* follow, const uint64_t* pred,
+                          const int32_t* pat_len, int n_expressions, const int32_t* jobs, int n_jobs, int sigma, int max_hits, int32_t* best,
+                          int32_t* n_hits, int32_t* hits, omp_stream_t s);
+
 /* ---- page text alignment: the optimal edit script of whole pages ----
  * The script behind omp_page_edit_distance's number: a is the prediction (rows i), b the ground truth (columns j), D the Levenshtein
  * table with D[i][0] = i and D[0][j] = j.  The walk runs from (la, lb) to (0, 0) and takes the FIRST rule that applies:
