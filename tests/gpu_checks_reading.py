@@ -14,7 +14,9 @@ from advancedliteratemachinery_amd.utils import windows as WN
 from advancedliteratemachinery_amd.utils.parser import make_args
 from tests import reading_cases as RC
 
-GROUP_SIZES = (0, 1, 2, 63, 64, 65, 255, 256, 257, 513)   # the wave, the tile of 256 and the lines kernel's 512 from both sides
+GROUP_SIZES = (0, 1, 2, 63, 64, 65, 255, 256, 257, 513)   # the wave and the links kernel's tile of 256 from both sides, two tiles and a word
+LARGE_SIZES = (1023, 1024, 1025, 2049)                     # the lines kernel's 1024 threads from both sides, a third word for one thread
+LARGE_KINDS = ('rotated', 'ring', 'duplicates', 'rows')
 ASPECTS = ((256, 256), (256, 128), (37, 256), (1, 1))
 PARAMS = ((2000, 500, 500), (0, 0, 0), (10000, 10000, 10000))
 KINDS = ('rows', 'rotated', 'ring', 'random', 'duplicates', 'degenerate')
@@ -97,6 +99,12 @@ def check_reading_op():
             linked += int((want['succ'] >= 0).sum())
             lines += int(want['n_lines'].sum())
     out.append(rec('reading: the cases link words and cut cycles somewhere', 0 if linked > 1000 and lines > 1000 else 1, 0, '%d links, %d lines' % (linked, lines)))
+    # links + lines where a thread of the lines kernel owns a second and a third word: one content kind per group, default parameters
+    polys, gs, aspect = _case(np.random.RandomState(19), LARGE_SIZES, 4096, LARGE_KINDS)
+    links = RD.links_cpu(polys, gs, aspect, grid=4096)
+    want = RD.resolve_cpu(links[0], links[1], gs, RD.features_cpu(OV._check_polys(polys, 4096), RD._aspect_per_word(gs, aspect)))   # lines_cpu, its links shared
+    got = RD.ReadingOrder(DEV, 4096).run(polys, gs, aspect, want_links=True)
+    _compare('reading[grid=4096 groups=%s]' % (list(LARGE_SIZES),), got, want, links, out, '%d words, %d lines' % (len(polys), int(want['n_lines'].sum())))
     # the ring alone: one cycle, cut in front of word 0
     got = RD.ReadingOrder(DEV, 1000).run(RC.ring(), [0, 10], [[256, 256]])
     out.append(rec('reading: ring of 10 is one line from word 0', int(got['line_pos'].tolist() != list(range(10))) + int(got['n_lines'].tolist() != [1]), 0))
@@ -119,6 +127,192 @@ def check_reading_largest_group():
     _compare('reading[n=8192]', got, want, links, out, '%d lines' % int(want['n_lines'][0]))
     from tests.gpu_checks import rec
     out.append(rec('reading[n=8192] the page is 128 lines of 64', 0 if int(want['n_lines'][0]) == 128 and int(want['line_pos'].max()) == 63 else 1, 0))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# line resolution alone, on planted links: reading_lines_kernel with 2 .. 8 words per thread
+# ---------------------------------------------------------------------------------------------------------------------------------
+RESOLUTION_SIZES = (1023, 1024, 1025, 2048, 2049, 4097, 8191, 8192)       # 1 | 1 | 2 ragged | 2 | 3 ragged | 5 ragged | 8 ragged | 8 words per thread
+MIXED_SIZES = (1025, 0, 1, 8192, 1023)                                    # the LDS layout follows cap = 8192 while ng differs
+STRUCTURES = ('chain', 'cycle', 'many', 'stars equal', 'stars distinct', 'extremes', 'ignored')
+COST_MAX = 2 ** 43 - 1                                                    # the bound of csrc/reading.hip's header
+
+
+def _segments(n, rng):
+    """lengths and kinds that fill n: cycles of exactly 1023, 1024 and 1025 where they fit beside a 2-cycle, two 2-cycles, then short
+    cycles (2 or more members) and paths in turn -> [(length, is_cycle)]"""
+    segs, used = [], 0
+    for c in (1023, 1024, 1025):
+        if used + c + 2 <= n:
+            segs.append((c, True))
+            used += c
+    for _ in range(2):
+        if used + 2 <= n:
+            segs.append((2, True))
+            used += 2
+    while used < n:
+        m = min(n - used, int(rng.randint(1, 40)))
+        segs.append((m, m >= 2 and len(segs) % 2 == 0))
+        used += m
+    return segs
+
+
+def _star(succ, cost, members, equal):
+    """members[1:] all claim members[0]; equal costs (the lowest index wins), or distinct ones with the least at the highest index"""
+    b, claim = int(members[0]), np.sort(members[1:])
+    succ[claim] = b
+    cost[claim] = 7 if equal else 1000 + (claim.max() - claim)
+
+
+def group_links(kind, n, rng):
+    """one group's planted links, local indices -> (succ0 int64 [n], cost0 int64 [n], ignored bool [n]: entries the kernel is documented
+    to ignore; with kind 'ignored' some point outside 0 .. n - 1, which the caller turns into indices of a neighbouring group)"""
+    succ = np.full(n, -1, dtype=np.int64)
+    cost = rng.randint(0, COST_MAX + 1, n, dtype=np.int64)
+    ignored = np.zeros(n, dtype=bool)
+    if n == 0:
+        return succ, cost, ignored
+    perm = rng.permutation(n)
+    if kind in ('chain', 'cycle'):
+        succ[perm[:-1]] = perm[1:]
+        if kind == 'cycle' and n > 1:
+            succ[perm[-1]] = perm[0]
+    elif kind in ('many', 'ignored'):
+        at = 0
+        for m, cyc in _segments(n, rng):
+            seg = perm[at:at + m]
+            succ[seg[:-1]] = seg[1:]
+            if cyc:
+                succ[seg[-1]] = seg[0]
+            at += m
+        if kind == 'ignored' and n >= 8:
+            pick = rng.permutation(n)[:max(3, n // 6)]
+            third = len(pick) // 3
+            succ[pick[:third]] = pick[:third]                                # a word naming itself
+            succ[pick[third:2 * third]] = np.where(rng.rand(third) < 0.5, -2 - rng.randint(0, 9, third), n + rng.randint(0, 9, third))   # outside its group
+            succ[pick[2 * third:]] = -1                                      # no successor, and a garbage cost
+            cost[pick[2 * third:]] = rng.randint(-2 ** 62, 2 ** 62, len(pick) - 2 * third, dtype=np.int64)
+            ignored[pick[:2 * third]] = True
+    else:                                                                    # stars of 2, 64 and 1025 claimants; the rest is one chain
+        at = 0
+        for m in (2, 64, 1025):
+            if at + m + 1 <= n:
+                _star(succ, cost, perm[at:at + m + 1], kind == 'stars equal')
+                if kind == 'extremes':
+                    cost[perm[at + 1:at + m + 1]] = np.where(rng.rand(m) < 0.5, 0, COST_MAX)
+                at += m + 1
+        rest = perm[at:]
+        succ[rest[:-1]] = rest[1:]
+        if kind == 'extremes':
+            cost[rest] = np.where(rng.rand(len(rest)) < 0.5, 0, COST_MAX)
+            if len(rest) > 1:
+                succ[rest[-1]] = perm[0]                                     # a chain that ends in a star's centre: one more claimant
+    return succ, cost, ignored
+
+
+def planted_call(kind, sizes, rng):
+    """-> (succ0 int32 [N] global, cost0 int64 [N], the same links with the ignored entries set to -1)"""
+    gs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    N = int(gs[-1])
+    succ0, clean, cost0 = np.full(N, -1, np.int64), np.full(N, -1, np.int64), np.zeros(N, np.int64)
+    for g, n in enumerate(sizes):
+        s, c, ign = group_links(kind, n, rng)
+        lo = int(gs[g])
+        inside = (s >= 0) & (s < n)
+        # -2, -3, ...: the words in front of the group, from its neighbour's last; n, n + 1, ...: the words behind it.  At the ends of a
+        # call these leave the call altogether (below 0 or from N on): the kernel compares them and never uses them as an index
+        glob = np.where(s == -1, -1, np.where(s < -1, lo + s + 1, lo + s))
+        assert (ign | inside | (s == -1)).all() and not (ign & (glob >= lo) & (glob < lo + n) & (glob != np.arange(lo, lo + n))).any()
+        succ0[lo:lo + n] = glob
+        clean[lo:lo + n] = np.where(ign, -1, glob)
+        cost0[lo:lo + n] = c
+    assert succ0.max() < 2 ** 31 and (clean < N).all()
+    return succ0.astype(np.int32), cost0, clean.astype(np.int32)
+
+
+def _cycle_lengths(succ):
+    """the lengths of the cycles of links without contests (every word named at most once)"""
+    succ = [int(v) for v in succ]
+    seen, out = [False] * len(succ), []
+    for i in range(len(succ)):
+        j, m = i, 0
+        while j >= 0 and not seen[j]:
+            seen[j] = True
+            j, m = succ[j], m + 1
+        if j == i and m:
+            out.append(m)
+    return out
+
+
+def _resolution_words(content, sizes, rng, grid):
+    N = int(sum(sizes))
+    if content == 'identical':                                               # every line ordering ties down to the head's index
+        return np.tile(rng.randint(0, grid, size=(1, 32)), (N, 1)).astype(np.int32)
+    if content == 'bottom':                                                  # every y at the last bin: the largest sum a line can hold
+        p = rng.randint(0, grid, size=(N, 32)).astype(np.int32)
+        p[:, 1::2] = grid - 1
+        return p
+    return rng.randint(0, grid, size=(N, 32)).astype(np.int32)
+
+
+def _resolution_calls():
+    """(name, structure, content, sizes, aspect)"""
+    for n in RESOLUTION_SIZES:
+        for kind in STRUCTURES:
+            yield 'n=%d' % n, kind, 'random', (n,), ((256, 256),)
+        for kind in ('chain', 'cycle', 'many', 'stars equal'):
+            yield 'n=%d' % n, kind, 'identical', (n,), ((37, 256),)
+    yield 'n=8192 every y = 4095', 'chain', 'bottom', (8192,), ((256, 256),)
+    for kind in STRUCTURES:
+        yield 'groups=%s' % (list(MIXED_SIZES),), kind, 'random', MIXED_SIZES, tuple(ASPECTS[g % 4] for g in range(len(MIXED_SIZES)))
+
+
+def check_reading_resolution():
+    """omp_reading_lines on links that no geometry produces == resolve_cpu on the same links, on succ, pred, line, line_pos, rank and
+    n_lines: one chain through a whole group, the chain closed into a cycle, many cycles and paths (2-cycles, cycles of exactly 1023,
+    1024 and 1025), stars of 2, 64 and 1025 claimants, the cost extremes 0 and 2^43 - 1; groups of 1023 .. 8192 words alone and mixed
+    in one call.  The kernel is documented to ignore a word naming itself, a successor outside its group and succ0 = -1 whatever its
+    cost; resolve_cpu is only defined for in-group links, so the expectation is resolve_cpu with exactly those entries set to -1."""
+    from advancedliteratemachinery_amd import ops
+    from tests.gpu_checks import DEV, rec
+    grid = 4096
+    out = []
+    rng = np.random.RandomState(21)
+    seen = dict(longest=0, lines=0, losers=0, cut=0, ignored=0, big_cycles=set())
+    for name, kind, content, sizes, aspect in _resolution_calls():
+        gs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        N, G = int(gs[-1]), len(sizes)
+        aspect = np.asarray(aspect, dtype=np.int32).reshape(G, 2)
+        polys = _resolution_words(content, sizes, rng, grid)
+        succ0, cost0, clean = planted_call(kind, sizes, rng)
+        want = RD.resolve_cpu(clean, cost0, gs, RD.features_cpu(polys, RD._aspect_per_word(gs, aspect)))
+        host = np.concatenate([gs, aspect.reshape(-1)]).astype(np.int32)
+        d_polys, tables = torch.from_numpy(polys).to(DEV), torch.from_numpy(host).to(DEV)
+        ints = ops.reading_lines(d_polys, tables, host, G, grid, torch.from_numpy(succ0).to(DEV), torch.from_numpy(cost0).to(DEV))
+        got = dict(zip(OUTS, ops.split_reading_ints(ints.cpu().numpy(), N)))
+        bad = sum(int((got[k] != want[k]).sum()) if got[k].shape == want[k].shape else 10 ** 6 for k in OUTS)
+        out.append(rec('resolution[%s] %s, %s words: succ, pred, line, line_pos, rank, n_lines' % (name, kind, content), bad, 0,
+                       '%d lines, longest %d' % (int(want['n_lines'].sum()), int(want['line_pos'].max()) + 1)))
+        # what the reference says the planted links did
+        linked = clean >= 0
+        if kind == 'chain':
+            out.append(rec('precondition: resolution[%s] chain, %s words: one line through every group' % (name, content),
+                           int((want['n_lines'] != (np.diff(gs) > 0)).sum()) + int(int(want['line_pos'].max()) != max(sizes) - 1), 0))
+        if kind == 'cycle':
+            heads = [int(want['line_pos'][gs[g]]) for g in range(G) if sizes[g]]
+            out.append(rec('precondition: resolution[%s] cycle, %s words: one line per group, cut in front of its least index' % (name, content),
+                           int((want['n_lines'] != (np.diff(gs) > 0)).sum()) + int(any(heads)), 0))
+        seen['longest'] = max(seen['longest'], int(want['line_pos'].max()) + 1)
+        seen['lines'] += int(want['n_lines'].sum())
+        seen['losers'] += int((linked & (want['succ'] != clean)).sum()) if kind.startswith('stars') or kind == 'extremes' else 0
+        seen['cut'] += int((linked & (want['succ'] == -1)).sum()) if kind in ('cycle', 'many') else 0
+        seen['ignored'] += int((succ0 != clean).sum())
+        if kind == 'many':
+            seen['big_cycles'] |= set(c for c in _cycle_lengths(clean) if c > 1000)
+    ok = (seen['longest'] == 8192 and seen['losers'] > 5000 and seen['cut'] > 500 and seen['ignored'] > 1000 and seen['big_cycles'] == {1023, 1024, 1025})
+    out.append(rec('precondition: the planted links hold a line of 8192, lost contests, cut cycles of 1023 / 1024 / 1025 and ignored entries', 0 if ok else 1, 0,
+                   '%s' % (sorted(seen.items(), key=lambda kv: kv[0]),)))
     return out
 
 

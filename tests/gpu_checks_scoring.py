@@ -97,6 +97,73 @@ def check_match_op():
     return out
 
 
+LARGE_PAGES = ((40, 1100), (1100, 40), (300, 700))      # up to 18 words of the free set: a wave owns words w, w + 4, w + 8, ...
+
+
+def _stride_events(gt_det):
+    """the matched detections of one image at the reported threshold (the REFERENCE's gt_det) -> (matches taken out of a free-set word
+    >= 5, waves that take matches out of two or more different words of their own stride)"""
+    d = gt_det[gt_det >= 0].astype(np.int64)
+    words = d >> 6
+    return int((words >= 5).sum()), sum(1 for w in range(4) if len(set(words[words % 4 == w].tolist())) >= 2)
+
+
+def check_match_large():
+    """pages of (40, 1100), (1100, 40) and (300, 700) (ground truth, detections), built like the smaller ones: the three in one call at
+    n_thr = 2 against match_pages_cpu and, image by image, against the naive matcher (which is too slow for the sweep of 64); each
+    alone at n_thr = 64 against match_pages_cpu.  Preconditions from the reference: on the two pages with more than 256 detections some
+    combination matches out of a free-set word >= 5, and has a wave that matches out of two words of its own stride."""
+    from tests.gpu_checks import DEV, rec
+    from tests.scoring_cases import naive_match
+    out = []
+    grid = 1000
+    held = {size: False for size in LARGE_PAGES if size[1] > 256}
+
+    def events(name, want, case, sizes):
+        for g, size in enumerate(sizes):
+            lo = int(case['group_start'][g])
+            high, waves = _stride_events(want[2][lo:lo + size[0]])
+            if size in held:
+                held[size] = held[size] or (high > 0 and waves > 0)
+                out.append(rec('%s page %s: figures of the reference' % (name, size), 0, 0, '%d matches in words >= 5, %d waves with two words' % (high, waves)))
+
+    # the three pages in one call, n_thr = 2: the specification and the naive matcher
+    case = pages(120, LARGE_PAGES, grid, 2)
+    dev = _Device(case, grid, DEV)
+    gs = case['group_start']
+    for t_iou, t_dc, report in ((500, 500, 0), (1000, 500, 1), (1, 1000, 1), (1000, 1, -1)):
+        name = 'match[G=3 %s n_thr=2] t_iou=%d t_dc=%d report=%d' % (list(LARGE_PAGES), t_iou, t_dc, report)
+        want = SC.match_pages_cpu(dev.flat, dev.ist, gs, case['n_gt'], case['gt_dc'], case['text'], case['level'], 2, t_iou, t_dc, report)
+        got = dev.match(2, t_iou, t_dc, report)
+        out.append(rec(name + ': counts, det_gt, gt_det', _diff(got, want), 0, '%d polygons, %d matched over the sweep' % (dev.n, int(want[0][..., 2].sum()))))
+        bad = 0
+        for g, (m, nd) in enumerate(LARGE_PAGES):
+            lo, hi = int(gs[g]), int(gs[g + 1])
+            mat = dev.flat[int(dev.ist[g]):int(dev.ist[g + 1])].reshape(hi - lo, hi - lo)
+            naive = naive_match(mat, m, case['gt_dc'][lo:hi], case['text'][lo:hi], case['level'][lo:hi], 2, t_iou, t_dc, report)
+            bad += _diff((got[0][g], got[1][lo + m:hi], got[2][lo:lo + m]), naive)
+        out.append(rec(name + ': the device against the naive matcher, image by image', bad, 0))
+        if report >= 0:
+            events(name, want, case, LARGE_PAGES)
+    # each page alone under the sweep of 64
+    for c, size in enumerate(LARGE_PAGES):
+        case = pages(130 + c, (size,), grid, 64)
+        dev = _Device(case, grid, DEV)
+        for t_iou, t_dc, report in ((500, 500, 0), (1000, 500, 63), (1, 1000, 40), (1000, 1, -1)):
+            name = 'match[G=1 %s n_thr=64] t_iou=%d t_dc=%d report=%d' % (size, t_iou, t_dc, report)
+            want = SC.match_pages_cpu(dev.flat, dev.ist, case['group_start'], case['n_gt'], case['gt_dc'], case['text'], case['level'], 64, t_iou, t_dc, report)
+            got = dev.match(64, t_iou, t_dc, report)
+            out.append(rec(name + ': counts, det_gt, gt_det', _diff(got, want), 0, '%d polygons, %d matched over the sweep' % (dev.n, int(want[0][..., 2].sum()))))
+            if report >= 0:
+                events(name, want, case, (size,))
+        r = SC.SpottingScorer(DEV, grid).run(case['polys'], case['group_start'], case['n_gt'], case['gt_dc'], case['text'], case['level'], 64, 500, 500, 0)
+        want = SC.match_pages_cpu(dev.flat, dev.ist, case['group_start'], case['n_gt'], case['gt_dc'], case['text'], case['level'], 64, 500, 500, 0)
+        out.append(rec('match[G=1 %s n_thr=64] SpottingScorer.run == match_pages_cpu' % (size,), _diff((r['counts'], r['det_gt'], r['gt_det']), want), 0))
+    for size, ok in held.items():
+        out.append(rec('precondition: page %s matches out of a free-set word >= 5, and one wave out of two words of its stride' % (size,), 0 if ok else 1, 0))
+    return out
+
+
 def check_chunked():
     """40 small images, the entry cap lowered so that they split into at least 3 chunks == pair_overlap_cpu + match_pages_cpu unchunked"""
     from tests.gpu_checks import DEV, rec

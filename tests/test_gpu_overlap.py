@@ -27,8 +27,19 @@ def test_polygon_overlap_and_keep_equal_the_specification(C):
     _assert_all(C.check_overlap_op())
 
 
+@pytest.mark.parametrize('call', [0, 1, 2], ids=['4097', '4032-4096-4161', '8192'])
+@pytest.mark.timeout(300, method='thread')
+def test_polygon_overlap_and_keep_above_4096_polygons(C, call):
+    """groups of 4097 | 4032, 4096, 4161 | 8192 on grid 4096: duplicates and chains planted across position 4096, so that the keep
+    kernel's second wave hands over its word, takes kept rows from wave 0 and assigns owners; (iou, 500) in identity, reversed and
+    random order, (iomin, 1000) random, (iou, 1) identity; every mask word up to 4161, sampled mask rows at 8192"""
+    _assert_all(C.check_overlap_large_groups(call))
+
+
 @pytest.mark.timeout(120, method='thread')
 def test_polygon_overlap_refuses_with_error_codes(C):
+    """the entry points' error codes, and what only the device tables show: a group of 8193 and a group whose rows do not fit the mask
+    come back as kept = -1 with owner = identity, beside a group that is processed"""
     _assert_all(C.check_overlap_refusals())
 
 

@@ -29,6 +29,13 @@ def test_spotting_match_equals_the_specification(C):
     _assert_all(C.check_match_op())
 
 
+@pytest.mark.timeout(300, method='thread')
+def test_spotting_match_beyond_one_stride_of_the_free_set(C):
+    """pages of (40, 1100), (1100, 40) and (300, 700): up to 18 words of the free set, so that a wave matches out of its second and later
+    words; one call of the three at n_thr = 2 against match_pages_cpu and the naive matcher, each alone at n_thr = 64"""
+    _assert_all(C.check_match_large())
+
+
 @pytest.mark.timeout(120, method='thread')
 def test_a_chunked_call_equals_the_unchunked_specification(C):
     _assert_all(C.check_chunked())
