@@ -166,6 +166,7 @@ _SIGS = {
     'omp_page_search': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64] + [c_void_p] * 4),
     'omp_page_pattern_search': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64] + [c_void_p] * 4),
     'omp_page_regex_search': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
+    'omp_page_regex_fuzzy_search': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     'omp_reading_links': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 3),
     'omp_reading_lines': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 9),
     'omp_reading_blocks': (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 9),

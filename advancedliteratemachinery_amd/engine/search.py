@@ -1,7 +1,7 @@
 """Page search on records: where a phrase (find_text: DESIGN.md section 25, utils/page_search.py, csrc/page_search.hip) or a shape such as a
 date, an amount or an id (find_pattern: DESIGN.md section 29, utils/page_pattern.py, csrc/page_pattern.hip; find_regex: the same with
-groups, alternation and real loops, exactly: DESIGN.md section 30, utils/page_regex.py, csrc/page_regex.hip) stands on a read page, which
-words carry it and how badly it was misread."""
+groups, alternation and real loops, exactly: DESIGN.md section 30, utils/page_regex.py, csrc/page_regex.hip; with max_dist or max_ratio
+within up to 4 errors: section 31, csrc/page_regex_fuzzy.hip) stands on a read page, which words carry it and how badly it was misread."""
 import numpy as np
 
 
@@ -149,12 +149,17 @@ def find_pattern(records, patterns, field='rec', max_dist=None, max_ratio=0.0, s
     return out
 
 
-def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_hits=16, searcher=None, device=None):
+def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_hits=16, searcher=None, device=None, max_dist=None, max_ratio=0.0):
     """records: as find_text takes them, IN THE ORDER TO BE READ.  expressions: a list for all images, or one list (not tuple) per image;
     an expression is a string in the syntax of utils.page_regex.parse_regex (find_pattern's atoms with groups, `|` at any depth and the
     quantifiers ? * + {n} {a,b} {a,}; `*`, `+` and `{a,}` are real loops) or a (name, string) tuple.  Every image becomes one text
-    (page_index); `normalise` is applied to the page words ONLY, never to an expression.  An expression is matched exactly: there is no
-    tolerance.
+    (page_index); `normalise` is applied to the page words ONLY, never to an expression.  With the defaults (max_dist=None, max_ratio=0.0)
+    an expression is matched exactly, through a RegexSearcher, and the result dicts are those described below.
+    WITH ERRORS: when max_dist or max_ratio is given, an expression whose shortest word holds min_len characters gets the tolerance
+    k = utils.page_regex.regex_tolerance(min_len, max_dist, max_ratio) <= min(min_len - 1, 4) (max_dist alone bounds k by max_dist,
+    max_ratio alone by the ratio, both by the lesser), ALL jobs (those with k = 0 included) go
+    through one utils.page_regex.FuzzyRegexSearcher.run (searcher= then takes one, or a HostFuzzyRegexSearcher), every result dict gains
+    `k`, best is the least distance within k or None, and a hit's dist is its distance (`(EUR|USD) ?\\d+` finds `EUP 120` at dist 1).
     searcher: a utils.page_regex.RegexSearcher, or anything with its `run` (HostRegexSearcher: the specification); default: one on
     `device` (default 'cuda').  All images and expressions go through ONE searcher.run.
     -> per image a list with one dict per expression: pattern (the string), name (None for a bare string), P (its positions), best (0
@@ -177,6 +182,7 @@ def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_h
     else:
         lists = [expressions] * len(records)
     pages = [page_index(recs, field, sep, normalise) for recs in records]
+    fuzzy = max_dist is not None or (max_ratio is not None and float(max_ratio) != 0.0)
     table, parsed, jobs, named = {}, [], [], []
     for b, ps in enumerate(lists):
         for p in ps:
@@ -192,12 +198,22 @@ def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_h
     if not jobs:
         return out
     pool, page_off, page_len, masks, first, last, follow, pred, pat_len, _ = PR.encode_regex([p[0] for p in pages], parsed)
-    if searcher is None:
-        searcher = PR.RegexSearcher('cuda' if device is None else device)
-    res = searcher.run(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, np.asarray(jobs, dtype=np.int32), int(max_hits))
+    if fuzzy:
+        ratio = None if max_dist is not None and not max_ratio else max_ratio  # max_dist alone: the ratio's default of 0 is no bound
+        k = [PR.regex_tolerance(r.min_len, max_dist, ratio) for r in parsed]
+        if searcher is None:
+            searcher = PR.FuzzyRegexSearcher('cuda' if device is None else device)
+        res = searcher.run(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, np.asarray(jobs, dtype=np.int32), np.asarray(k, dtype=np.int32),
+                           int(max_hits))
+    else:
+        if searcher is None:
+            searcher = PR.RegexSearcher('cuda' if device is None else device)
+        res = searcher.run(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, np.asarray(jobs, dtype=np.int32), int(max_hits))
     for at, ((b, q), (name, src)) in enumerate(zip(jobs, named)):
         text, w_start, w_len = pages[b]
         dist, end = (int(v) for v in res['best'][at])
         hits, dropped = _carried(records[b], text, w_start, w_start + w_len, res['hits'][at])
         out[b].append(dict(pattern=src, name=name, P=parsed[q].P, best=None if end == 0 else dist, n_hits=int(res['n_hits'][at]), dropped=dropped, hits=hits))
+        if fuzzy:
+            out[b][-1]['k'] = k[q]
     return out

@@ -1089,6 +1089,37 @@ def page_regex_search(pool, pool_bytes, page_off, page_len, masks, first, last, 
     return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
 
 
+def page_regex_fuzzy_search(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, k, jobs, sigma, max_hits, best=None,
+                            n_hits=None, hits=None):
+    """omp_page_regex_fuzzy_search (csrc/page_regex_fuzzy.hip; utils/page_regex.py holds the specification): the inputs of page_regex_search
+    and k int32 [Q], one tolerance 0 .. 4 per expression; the kernel needs no scratch -> (best int32 [J, 2] = (the least distance, the least
+    end that attains it) or (k + 1, 0), n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, dist, start), -1 where there is no hit);
+    n_hits = -1 for a job whose lengths, ranges, automaton words or tolerance are out of bounds."""
+    P, Q, J, H, S = int(page_len.numel()), int(pat_len.numel()), int(jobs.numel()) // 2, int(max_hits), int(sigma)
+    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
+                                  ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('first', first, torch.int64, Q), ('last', last, torch.int64, Q),
+                                  ('follow', follow, torch.int64, 64 * Q), ('pred', pred, torch.int64, 64 * Q), ('pat_len', pat_len, torch.int32, Q),
+                                  ('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J)):
+        if t is None:
+            raise ValueError('%s is missing' % name)
+        _c(t, name)
+        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if jobs.numel() != 2 * J:
+        raise ValueError('jobs must hold (page, expression) pairs, got %d integers' % jobs.numel())
+    outs = []
+    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
+        if t is None:
+            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
+        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
+        outs.append(t)
+    rc = _lib.lib().omp_page_regex_fuzzy_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(masks), ptr(first), ptr(last), ptr(follow),
+                                                ptr(pred), ptr(pat_len), ptr(k), Q, ptr(jobs), J, S, H, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
+    _lib.check(rc, 'omp_page_regex_fuzzy_search')
+    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+
+
 def _reading_tables(polys, tables, host_tables, n_groups):
     N, G = int(polys.shape[0]), int(n_groups)
     for name, tt, numel in (('polys', polys, 32 * N), ('tables', tables, 3 * G + 1)):

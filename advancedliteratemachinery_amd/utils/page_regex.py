@@ -27,6 +27,22 @@ Split       ends_chunked(): the kernel's way over a page.  The step is linear ov
             speculative pass), then takes the exit state of the lane before it and runs the bits it has not carried yet through its
             chunk WITHOUT injecting first, until no lane gets a new bit.
 Limits      a page 0 .. 65535 characters, 1 .. 2^20 jobs a call, 1 .. 64 hits kept per job.
+
+With errors (csrc/page_regex_fuzzy.hip, omp_page_regex_fuzzy_search, equals fuzzy_search_cpu on every integer):
+Tolerance   k = regex_tolerance(min_len, max_dist, max_ratio) = min(page_pattern.tolerance(min_len, ...), K_MAX), min_len the length of the
+            shortest word of the language: k <= min_len - 1, so deleting the whole expression never qualifies.
+Rows        R_0 .. R_k, one word each.  Bit p of R_i after column j: some t[s:j] aligns, with at most i insertions, deletions and
+            substitutions of cost 1, to a path of the automaton from first that ends at position p.  Fol(X) = Follow(X) | first:
+              before any text  R_0 = 0, R_i = Fol(R_{i-1})
+              column j         R'_0 = Fol(R_0) & B
+                               R'_i = (Fol(R_i) & B) | Fol(R_{i-1}) | R_{i-1} | Fol(R'_{i-1})     match, substitution, insertion, deletion
+            v_j = the least i with R'_i & last != 0, else k + 1; v_0 = k + 1.  dist_py is the same on sets of positions.
+A hit       page_search.hit_ends(v, k); best = (min v, the least end that attains it) or (k + 1, 0); hits = (end, dist, start).
+start       fuzzy_start(): the least s whose anchored distance of t[s:end] to the language equals dist: the same step backwards from
+            `end` with rows 0 .. dist, Pred for Follow and last for first, the injection of row i gated by a flag G_i (the walk's own
+            start state: 1 at `end`, G'_0 = 0, G'_i = G_{i-1}: it has consumed that many characters as insertions).  No span cap.
+Split       dist_chunked(): the step is R' = L(R) | constant with L linear over union, so ends_chunked's speculative pass and carry
+            rounds carry over with k + 1 words where there was one.
 """
 import re
 from collections import namedtuple
@@ -41,6 +57,7 @@ POS_MAX = 64                    # positions an expression (csrc/page_regex.hip: 
 CHUNK = 128                     # text columns per lane (csrc/page_regex.hip: PR_CHUNK)
 LANES = 64
 ROUND = CHUNK * LANES           # text columns per round of the wave
+K_MAX = 4                       # errors at the most under an expression (csrc/page_regex_fuzzy.hip: PF_K_MAX): k + 1 <= 5 rows in registers
 _FULL = (1 << 64) - 1
 
 
@@ -49,7 +66,7 @@ _FULL = (1 << 64) - 1
 # ---------------------------------------------------------------------------------------------
 class Regex(object):
     """a parsed expression: src, atoms (one re source per position), P, first, last (the bit words), follow and pred (uint64 [64], rows
-    at or above P zero; pred is follow transposed)"""
+    at or above P zero; pred is follow transposed), min_len (the length of the shortest word of the language)"""
 
     def __init__(self, src, atoms, first, last, follow):
         self.src, self.atoms = src, tuple(atoms)
@@ -58,6 +75,7 @@ class Regex(object):
         rows = [int(f) for f in follow] + [0] * (POS_MAX - len(follow))
         self.follow = np.asarray(rows, dtype=np.uint64)
         self.pred = np.asarray(_transpose(rows), dtype=np.uint64)
+        self.min_len = min_len(self.first, self.last, rows)
 
     def __repr__(self):
         return 'Regex(%r, P=%d)' % (self.src, self.P)
@@ -79,6 +97,22 @@ def _bits(x):
     while x:
         yield (x & -x).bit_length() - 1
         x &= x - 1
+
+
+def min_len(first, last, follow):
+    """the length of the shortest word of the language: a breadth-first walk from first through follow to last.  POS_MAX + 1 when no
+    position of last can be reached (the language is empty; parse_regex builds no such automaton)"""
+    first, last = int(first), int(last)
+    seen, front, depth = 0, first, 1
+    while front:
+        if front & last:
+            return depth
+        seen |= front
+        nxt = 0
+        for i in _bits(front):
+            nxt |= int(follow[i])
+        front, depth = nxt & ~seen, depth + 1
+    return POS_MAX + 1
 
 
 _BRACE = re.compile(r'\{(\d*)(,?)(\d*)\}')
@@ -548,4 +582,261 @@ class RegexSearcher(_DeviceStage):
         if (res['n_hits'] < 0).any():
             raise RuntimeError('omp_page_regex_search refused a job (a length above the limits, a range outside the pool, or first, last, follow '
                                'or pred words with bits or rows at or above P)')
+        return res
+
+
+# ---------------------------------------------------------------------------------------------
+# with errors: the specification
+# ---------------------------------------------------------------------------------------------
+def regex_tolerance(shortest, max_dist=None, max_ratio=0.0):
+    """the tolerance k of an expression whose shortest word holds `shortest` characters (Regex.min_len):
+    min(page_pattern.tolerance(shortest, max_dist, max_ratio), K_MAX), so k <= shortest - 1"""
+    from .page_pattern import tolerance
+    return min(tolerance(min(int(shortest), POS_MAX), max_dist, max_ratio), K_MAX)
+
+
+def _tolerance_of(k):
+    k = int(k)
+    if not 0 <= k <= K_MAX:
+        raise ValueError('a tolerance is 0 .. %d, got %d' % (K_MAX, k))
+    return k
+
+
+def dist_py(tab, t, k, rows=False):
+    """v_0 .. v_n, clipped at k + 1, int32: sets of positions per row, no bit tricks -- the ground truth of the step with errors.
+    rows=True: -> (v, per column 0 .. n the k + 1 rows as frozensets)"""
+    k = _tolerance_of(k)
+    B = [frozenset(_bits(b)) for b in _classes(tab.mask, t)]
+    first, last = frozenset(_bits(tab.first)), frozenset(_bits(tab.last))
+    follow = [frozenset(_bits(f)) for f in tab.follow]
+
+    def fol(X):
+        reach = set(first)
+        for p in X:
+            reach |= follow[p]
+        return frozenset(reach)
+    R = [frozenset()]
+    for i in range(1, k + 1):
+        R.append(fol(R[i - 1]))                                               # deletions only
+    v, kept = [k + 1], [list(R)]
+    for b in B:
+        new = [fol(R[0]) & b]
+        for i in range(1, k + 1):
+            new.append((fol(R[i]) & b) | fol(R[i - 1]) | R[i - 1] | fol(new[i - 1]))
+        R = new
+        v.append(next((i for i in range(k + 1) if R[i] & last), k + 1))
+        kept.append(list(R))
+    v = np.asarray(v, dtype=np.int32)
+    return (v, kept) if rows else v
+
+
+def _fuzzy_step(T, inject, R, b):
+    """one column of the step on words: T the byte tables of follow (or pred), inject[i] the word injected into row i (first, or 0)"""
+    new = [(_move(T, R[0]) | inject[0]) & b]
+    for i in range(1, len(R)):
+        new.append(((_move(T, R[i]) | inject[i]) & b) | _move(T, R[i - 1]) | inject[i - 1] | R[i - 1] | _move(T, new[i - 1]) | inject[i - 1])
+    return new
+
+
+def _fuzzy_init(T, first, k):
+    R = [0]
+    for i in range(1, k + 1):
+        R.append(_move(T, R[i - 1]) | first)
+    return R
+
+
+def _value(R, last, k):
+    return next((i for i in range(k + 1) if R[i] & last), k + 1)
+
+
+def dist_cpu(tab, t, k):
+    """v_0 .. v_n, clipped at k + 1, int32, by the words: R'_0 = Fol(R_0) & B, R'_i = (Fol(R_i) & B) | Fol(R_{i-1}) | R_{i-1} | Fol(R'_{i-1})"""
+    k = _tolerance_of(k)
+    T, first, last = _byte_tables(tab.follow, tab.P), tab.first, tab.last
+    R = _fuzzy_init(T, first, k)
+    inject = [first] * (k + 1)
+    v = [k + 1]
+    for b in _classes(tab.mask, t):
+        R = _fuzzy_step(T, inject, R, b)
+        v.append(_value(R, last, k))
+    return np.asarray(v, dtype=np.int32)
+
+
+def fuzzy_start(tab, t, end, dist):
+    """the least s whose anchored distance of t[s:end] to the language equals dist (the longest match); (end, dist) must be a hit.  The
+    step backwards from `end` with rows 0 .. dist over pred; last is injected into row i while G_i holds: G_i = 1 at `end`, G'_0 = 0,
+    G'_i = G_{i-1} after every character"""
+    end, dist = int(end), int(dist)
+    if not 0 <= dist <= K_MAX:
+        raise ValueError('a distance is 0 .. %d, got %d' % (K_MAX, dist))
+    B = _classes(tab.mask, np.asarray(t, dtype=np.uint8).reshape(-1)[:end])
+    T, first, last = _byte_tables(tab.pred, tab.P), tab.first, tab.last
+    R, G = _fuzzy_init(T, last, dist), [1] * (dist + 1)
+    s, found = end, None
+    while s > 0 and (any(R) or any(G)):
+        s -= 1
+        new_g = [0] + G[:-1]
+        b = B[s]
+        new = [(_move(T, R[0]) | (last if G[0] else 0)) & b]
+        for i in range(1, dist + 1):
+            below = _move(T, R[i - 1]) | (last if G[i - 1] else 0)
+            new.append(((_move(T, R[i]) | (last if G[i] else 0)) & b) | below | R[i - 1] | _move(T, new[i - 1]) | (last if new_g[i - 1] else 0))
+        R, G = new, new_g
+        if R[dist] & first:
+            found = s
+    if found is None:
+        raise AssertionError('column %d is no end at distance %d: the reverse walk found no start' % (end, dist))
+    return found
+
+
+def dist_chunked(tab, t, k, chunk=CHUNK, lanes=LANES):
+    """dist_cpu by the split the kernel runs.  Per round: lane l runs its chunk from the deletion-only rows (lane 0: from the exact exit
+    rows of the round before) with first injected, and keeps k + 1 end planes (plane i holds column j iff R_i & last != 0 there) and its
+    exit rows X.  Then, until no lane gets a new bit in any row: every lane l >= 1 that holds text takes the rows X of lane l - 1, keeps
+    new_i = in_i & ~carried_i, runs them through the step WITHOUT any first, ORs the ends into the planes and the rows after its last
+    column into X, and leaves the chunk as soon as every row is 0.  v_j is the number of planes without column j.
+    -> (v int32 [n + 1], the carry rounds of every wave round)"""
+    k = _tolerance_of(k)
+    chunk, lanes = int(chunk), int(lanes)
+    B = _classes(tab.mask, t)
+    n = len(B)
+    T, first, last = _byte_tables(tab.follow, tab.P), tab.first, tab.last
+    with_first, without = [first] * (k + 1), [0] * (k + 1)
+    init = _fuzzy_init(T, first, k)
+    planes = np.zeros((k + 1, n + 1), dtype=bool)
+
+    def mark(R, col):
+        for i in range(k + 1):
+            if R[i] & last:
+                planes[i, col] = True
+    carry_in, rounds = list(init), []
+    for r0 in range(0, n, chunk * lanes):
+        lo = [min(r0 + l * chunk, n) for l in range(lanes + 1)]                   # lane l owns the characters lo[l] .. lo[l + 1] - 1
+        X = []
+        for l in range(lanes):
+            R = list(carry_in if l == 0 else init)
+            for c in range(lo[l], lo[l + 1]):
+                R = _fuzzy_step(T, with_first, R, B[c])
+                mark(R, c + 1)
+            X.append(R)
+        carried, count = [[0] * (k + 1) for _ in range(lanes)], 0
+        while True:
+            new = [[0] * (k + 1)] + [[X[l - 1][i] & ~carried[l][i] if lo[l + 1] > lo[l] else 0 for i in range(k + 1)] for l in range(1, lanes)]
+            if not any(any(r) for r in new):
+                break
+            count += 1
+            for l in range(1, lanes):
+                C = new[l]
+                carried[l] = [a | b for a, b in zip(carried[l], C)]
+                for c in range(lo[l], lo[l + 1]):
+                    if not any(C):
+                        break
+                    C = _fuzzy_step(T, without, C, B[c])
+                    mark(C, c + 1)
+                X[l] = [a | b for a, b in zip(X[l], C)]
+        rounds.append(count)
+        carry_in = X[lanes - 1]
+    return (k + 1 - planes.sum(axis=0)).astype(np.int32), rounds
+
+
+def _check_fuzzy(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits):
+    out = _check_search(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits)
+    first, last, follow = out[4], out[5], out[6]
+    k = np.asarray(k, dtype=np.int64).reshape(-1)
+    if k.size != first.size:
+        raise ValueError('k holds one entry per expression, got %d for %d' % (k.size, first.size))
+    if k.size and ((k < 0).any() or (k > K_MAX).any()):
+        raise ValueError('a tolerance is outside 0 .. %d' % K_MAX)
+    # k >= min_len iff a word of at most k <= K_MAX characters exists: the positions reached by exactly `depth` characters, all expressions at once
+    front, top = first.copy(), int(k.max()) if k.size else 0
+    for depth in range(1, top + 1):
+        short = (k >= depth) & ((front & last) != 0)
+        if short.any():
+            q = int(np.flatnonzero(short)[0])
+            raise ValueError('expression %d: the tolerance %d is not below the length of its shortest word, %d' % (q, k[q], depth))
+        nxt = np.zeros_like(front)
+        for i in range(int(out[8].max())):
+            nxt |= np.where((front >> np.uint64(i)) & np.uint64(1) != 0, follow[:, i], np.uint64(0))
+        front = nxt
+    return out[:10] + [k.astype(np.int32), out[10]]
+
+
+def fuzzy_search_cpu(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits):
+    """the definition with errors, for the flat inputs omp_page_regex_fuzzy_search takes; k int32 [Q], one tolerance per expression
+    -> dict(best int32 [J, 2] = (the least distance, the least end that attains it) or (k + 1, 0), n_hits int32 [J], hits int32
+    [J, max_hits, 3] = (end, dist, start), -1 where there is no hit)"""
+    pool, po, pl, masks, first, last, follow, pred, P, jobs, k, H = _check_fuzzy(pool, page_off, page_len, masks, first, last, follow, pred,
+                                                                                 pat_len, jobs, k, max_hits)
+    J = jobs.shape[0]
+    best = np.zeros((J, 2), dtype=np.int32)
+    n_hits = np.zeros(J, dtype=np.int32)
+    hits = np.full((J, H, 3), -1, dtype=np.int32)
+    done, tabs = {}, {}
+    for j, (p, q) in enumerate(jobs.tolist()):
+        key = (po[p], pl[p], q)
+        if key not in done:
+            if q not in tabs:
+                tabs[q] = tables(masks, first, last, follow, pred, P, q)
+            t = pool[po[p]:po[p] + pl[p]]
+            kq = int(k[q])
+            v = dist_cpu(tabs[q], t, kq)
+            end = int(np.argmin(v))                                           # the least j that attains the minimum; v_0 = k + 1
+            ends = hit_ends(v, kq)
+            rows = [(int(e), int(v[e]), fuzzy_start(tabs[q], t, int(e), int(v[e]))) for e in ends[:H].tolist()]
+            done[key] = ((int(v[end]), end), int(ends.size), rows)
+        b, c, rows = done[key]
+        best[j] = b
+        n_hits[j] = c
+        if rows:
+            hits[j, :len(rows)] = rows
+    return dict(best=best, n_hits=n_hits, hits=hits)
+
+
+class HostFuzzyRegexSearcher(object):
+    """FuzzyRegexSearcher's `run` from the specification (fuzzy_search_cpu): what the device stage must equal"""
+
+    def __init__(self):
+        self.calls = 0
+
+    def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits):
+        self.calls += 1
+        return fuzzy_search_cpu(pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits)
+
+
+class FuzzyRegexSearcher(_DeviceStage):
+    """fuzzy_search_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_regex_fuzzy_search launch per
+    JOBS_MAX jobs (the kernel needs no scratch), and ONE download of best, n_hits and hits.  There is no CPU fallback:
+    HostFuzzyRegexSearcher is the specification."""
+    HOST = 'HostFuzzyRegexSearcher'
+
+    def __init__(self, device):
+        super().__init__(device, 0)
+
+    def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits):
+        """the inputs of fuzzy_search_cpu -> the dict of fuzzy_search_cpu, as numpy.  sigma is masks.shape[1] - 1."""
+        import torch
+
+        from .. import ops
+        pool, po, pl, masks, first, last, follow, pred, P, jobs, k, H = _check_fuzzy(pool, page_off, page_len, masks, first, last, follow, pred,
+                                                                                     pat_len, jobs, k, max_hits)
+        sigma = masks.shape[1] - 1
+        J = jobs.shape[0]
+        self.calls += 1
+        parts = [(lo, min(lo + JOBS_MAX, J)) for lo in range(0, J, JOBS_MAX)]
+        self.chunks = len(parts)
+        if J == 0:
+            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
+        with torch.cuda.device(self.device):
+            i64 = lambda a: a.reshape(-1).view(np.int64)                        # noqa: E731  the 64-bit words travel as int64: the same bytes
+            (d_masks, d_first, d_last, d_follow, d_pred, d_po, d_pl, d_P, d_k, d_jobs), d_pool = self._upload(
+                (i64(masks), i64(first), i64(last), i64(follow), i64(pred), po, pl, P, k, jobs.reshape(-1)), pool)
+            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
+            for lo, hi in parts:
+                ops.page_regex_fuzzy_search(d_pool, pool.size, d_po, d_pl, d_masks, d_first, d_last, d_follow, d_pred, d_P, d_k, d_jobs[2 * lo:2 * hi], sigma,
+                                            H, best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
+            host = out.cpu().numpy()                                          # the one download
+        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
+        if (res['n_hits'] < 0).any():
+            raise RuntimeError('omp_page_regex_fuzzy_search refused a job (a length above the limits, a range outside the pool, first, last, '
+                               'follow or pred words with bits or rows at or above P, or k outside 0 .. %d)' % K_MAX)
         return res

@@ -889,6 +889,28 @@ int omp_page_regex_search(const uint8_t* pool, int64_t pool_bytes, const int32_t
                           const int32_t* pat_len, int n_expressions, const int32_t* jobs, int n_jobs, int sigma, int max_hits, int32_t* best,
                           int32_t* n_hits, int32_t* hits, omp_stream_t s);
 
+/* ---- page expressions with errors: a regular expression within k edits in the text of read pages ----
+ * The automaton and every table are omp_page_regex_search's; k holds one tolerance per expression.  Rows R_0 .. R_k, one 64-bit word each:
+ * bit p of R_i after column j says that some text[s, j) aligns, with at most i insertions, deletions and substitutions of cost 1, to a
+ * path of the automaton from first that ends at position p.  With Fol(X) = Follow(X) | first: before any text R_0 = 0, R_i = Fol(R_{i-1});
+ * at column j with B = masks[t_j]: R'_0 = Fol(R_0) & B, R'_i = (Fol(R_i) & B) | Fol(R_{i-1}) | R_{i-1} | Fol(R'_{i-1}).  v_j is the least
+ * i with R'_i & last != 0, else k + 1; v_0 = k + 1.  utils/page_regex.py holds the specification (dist_cpu, fuzzy_start,
+ * fuzzy_search_cpu); this entry point equals it on every integer.
+ *   pool .. pat_len, jobs, max_hits   as omp_page_regex_search takes them
+ *   k                  int32 [n_expressions]: 0 .. 4.  The caller keeps k below the length of the expression's shortest word (the host
+ *                      side checks it); the kernel does not need it
+ *   best               int32 [n_jobs, 2]: (the least v_j, the least column that attains it), or (k + 1, 0) when nothing is within k
+ *   n_hits             int32 [n_jobs]: the columns with v_j <= k, v_j <= v_{j-1} and (j == n or v_j < v_{j+1})
+ *   hits               int32 [n_jobs, H, 3] = (end, dist, start) of the first min(n_hits, H) hits in ascending end, the rest -1; start is
+ *                      the LEAST s whose anchored distance of text[s, end) to the language equals dist, found by a walk back without a cap
+ * OMP_ERR_INVALID, nothing launched: as omp_page_regex_search, and a null k.  REFUSED on the device (n_hits = -1, best and hits -1, nothing
+ *   of the pool read): everything omp_page_regex_search refuses there, and a k outside 0 .. 4.
+ * One launch, one wave per job, no scratch; no allocation, no synchronisation, no atomics: the hits do not depend on scheduling. */
+int omp_page_regex_fuzzy_search(const uint8_t* pool, int64_t pool_bytes, const int32_t* page_off, const int32_t* page_len, int n_pages,
+                                const uint64_t* masks, const uint64_t* first, const uint64_t* last, const uint64_t* follow, const uint64_t* pred,
+                                const int32_t* pat_len, const int32_t* k, int n_expressions, const int32_t* jobs, int n_jobs, int sigma,
+                                int max_hits, int32_t* best, int32_t* n_hits, int32_t* hits, omp_stream_t s);
+
 /* ---- page text alignment: the optimal edit script of whole pages ----
  * The script behind omp_page_edit_distance's number: a is the prediction (rows i), b the ground truth (columns j), D the Levenshtein
  * table with D[i][0] = i and D[0][j] = j.  The walk runs from (la, lb) to (0, 0) and takes the FIRST rule that applies:

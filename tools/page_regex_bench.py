@@ -4,7 +4,7 @@ family against omp_page_pattern_search at k = 0 on the same jobs.
 
   python tools/page_regex_bench.py [--pages 500] [--chars 5000] [--expressions 200] [--long_pages 16] [--long_chars 40000]
                                    [--long_expressions 1000] [--alphabet 60] [--max_hits 16] [--cpu_jobs 100] [--long_cpu_jobs 20]
-                                   [--repeats 5] [--warmup 1] [--out profiles/page_regex_bench.json]
+                                   [--repeats 5] [--warmup 1] [--k 0,1,2,4] [--out profiles/page_regex_bench.json]
 
 Seeded pages as tools/page_pattern_bench.py makes them: `chars` (+- 10 %) characters drawn from `alphabet` codes, a blank every 3 to 9
 characters; the codes 0 .. 9 are the digits, and every page gets runs of 150 to 400 digits planted at four places (longer than a lane's
@@ -16,7 +16,10 @@ characters; the codes 0 .. 9 are the digits, and every page gets runs of 150 to 
   never-dying ONE expression a.*b (a and b two codes of the alphabet): the carry never dies, the split degenerates to the serial run
 Per leg the tool times whole run calls (host clock; the call ends with the download), the kernel alone between device events on tables
 that are already on the device, and search_cpu on the first `cpu_jobs` jobs of a fixed random permutation; that host time is SCALED to
-the leg by the ratio of text columns and is stated as such.  One JSON document; every leg is also printed as it ends."""
+the leg by the ratio of text columns and is stated as such.  One JSON document; every leg is also printed as it ends.
+--k 0,1,2,4 adds, per leg and per value, the search WITH ERRORS: every expression gets min(k, min_len - 1), and the
+tool times one FuzzyRegexSearcher.run, omp_page_regex_fuzzy_search alone (stated as a ratio to omp_page_regex_search on the same jobs),
+for the flat family omp_page_pattern_search at the same tolerances, and checks fuzzy_search_cpu on a few jobs of the permutation."""
 import argparse
 import json
 import os
@@ -128,7 +131,53 @@ def make_never_dying(alphabet):
     return pack_words(masks, [_words(1, 4, [0b110, 0b110, 0])])
 
 
-def time_leg(name, texts, auto, max_hits, cpu_jobs, repeats, warmup, flat=None):
+def time_fuzzy(K, d, e, host, J, sigma, max_hits, exact_ms, pick, repeats, warmup):
+    """the leg's jobs with errors: every expression at min(K, min_len - 1).  d: the device tables of the exact leg; e: those of the flat
+    family's patterns or None; host: the numpy inputs"""
+    from advancedliteratemachinery_amd import ops
+    from advancedliteratemachinery_amd.utils import page_pattern as PP
+    from advancedliteratemachinery_amd.utils import page_regex as PR
+    pool, po, pl, masks, first, last, follow, pred, P, jobs = host
+    tol = np.asarray([min(K, PR.min_len(f, l, fo.tolist()) - 1) for f, l, fo in zip(first.tolist(), last.tolist(), follow)], dtype=np.int32)
+    sc = PR.FuzzyRegexSearcher('cuda')
+    run_ms, got = [], None
+    for i in range(warmup + repeats):
+        t0 = time.perf_counter()
+        got = sc.run(pool, po, pl, masks, first, last, follow, pred, P, jobs, tol, max_hits)
+        if i >= warmup:
+            run_ms.append((time.perf_counter() - t0) * 1e3)
+    dk = torch.from_numpy(tol).to('cuda')
+    outs = [torch.empty(n, dtype=torch.int32, device='cuda') for n in (2 * J, J, 3 * max_hits * J)]
+
+    def launch():
+        ops.page_regex_fuzzy_search(d[0], pool.size, d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], dk, d[9], sigma, max_hits, best=outs[0], n_hits=outs[1],
+                                    hits=outs[2])
+    ms = events(launch, repeats, warmup)
+    t0 = time.perf_counter()
+    want = PR.fuzzy_search_cpu(pool, po, pl, masks, first, last, follow, pred, P, jobs[pick], tol, max_hits)
+    cpu_ms = (time.perf_counter() - t0) * 1e3
+    doc = dict(k=K, tolerances={str(v): int((tol == v).sum()) for v in sorted(set(tol.tolist()))}, hits=int(got['n_hits'].sum()),
+               hits_with_errors=int((got['hits'][:, :, 1] > 0).sum()), run=spread(run_ms), kernel=dict(spread(ms), launches=1),
+               fuzzy_over_exact_kernel=round(statistics.median(ms) / exact_ms, 2),
+               host=dict(jobs=int(pick.size), ms=round(cpu_ms, 1)),
+               answers_equal_on_the_subsample=all(bool((got[key][pick] == want[key]).all()) for key in ('best', 'n_hits', 'hits')))
+    if e is not None:                                                       # the flat family through omp_page_pattern_search at the same tolerances
+        parts = PP.chunk_jobs(J, max_hits)
+        scratch = torch.empty(ops.page_pattern_scratch_bytes(max(hi - lo for lo, hi in parts), max_hits), dtype=torch.uint8, device='cuda')
+        outs2 = [torch.empty(n, dtype=torch.int32, device='cuda') for n in (2 * J, J, 3 * max_hits * J)]
+
+        def launch2():
+            for lo, hi in parts:
+                ops.page_pattern_search(d[0], pool.size, d[1], d[2], e[0], e[1], e[2], dk, d[9][2 * lo:2 * hi], sigma, max_hits, scratch,
+                                        best=outs2[0][2 * lo:2 * hi], n_hits=outs2[1][lo:hi], hits=outs2[2][3 * max_hits * lo:3 * max_hits * hi])
+        ms2 = events(launch2, repeats, warmup)
+        doc['page_pattern_same_k'] = dict(spread(ms2), launches=len(parts), fuzzy_regex_over_pattern=round(statistics.median(ms) / statistics.median(ms2), 2),
+                                          n_hits_equal=bool((outs[1] == outs2[1]).all().item()), hits_equal=bool((outs[2] == outs2[2]).all().item()),
+                                          best_equal=bool((outs[0] == outs2[0]).all().item()))
+    return doc
+
+
+def time_leg(name, texts, auto, max_hits, cpu_jobs, repeats, warmup, flat=None, ks=()):
     from advancedliteratemachinery_amd import ops
     from advancedliteratemachinery_amd.utils import page_pattern as PP
     from advancedliteratemachinery_amd.utils import page_regex as PR
@@ -184,6 +233,10 @@ def time_leg(name, texts, auto, max_hits, cpu_jobs, repeats, warmup, flat=None):
         doc['page_pattern_k0'] = dict(spread(ms2), launches=len(parts), regex_over_pattern=round(statistics.median(ms) / statistics.median(ms2), 2),
                                       n_hits_equal=bool((outs[1] == outs2[1]).all().item()), hits_equal=bool((outs[2] == outs2[2]).all().item()),
                                       best_equal=bool((outs[0] == outs2[0]).all().item()))
+    if ks:
+        e = None if flat is None else [i64(flat[0]), up(flat[1].view(np.int64)), up(flat[2])]
+        doc['with_errors'] = [time_fuzzy(K, d, e, (pool, po, pl, masks, first, last, follow, pred, P, jobs), J, sigma, max_hits, statistics.median(ms), pick[:4], repeats,
+                                         warmup) for K in ks]
     print(json.dumps(doc), flush=True)
     return doc
 
@@ -202,8 +255,12 @@ def main():
     p.add_argument('--long_cpu_jobs', type=int, default=20)
     p.add_argument('--repeats', type=int, default=5)
     p.add_argument('--warmup', type=int, default=1)
+    p.add_argument('--k', default='', help='comma-separated tolerances, e.g. 0,1,2,4: adds the search with errors to every leg')
     p.add_argument('--out', default=os.path.join('profiles', 'page_regex_bench.json'))
     a = p.parse_args()
+    ks = tuple(int(v) for v in a.k.split(',') if v.strip() != '')
+    if any(not 0 <= v <= 4 for v in ks):
+        raise SystemExit('--k takes tolerances 0 .. 4, got %r' % (a.k,))
     if not torch.cuda.is_available():
         raise SystemExit('page_regex_bench needs the GPU: a timing taken anywhere else says nothing')
     rng = np.random.RandomState(0)
@@ -213,13 +270,13 @@ def main():
     legs = []
     for what, texts, count, cpu_jobs in sets:
         auto, flat = make_flat(np.random.RandomState(1), texts, count, a.alphabet)
-        legs.append(time_leg('%s x %d flat shapes' % (what, count), texts, auto, a.max_hits, cpu_jobs, a.repeats, a.warmup, flat=flat))
+        legs.append(time_leg('%s x %d flat shapes' % (what, count), texts, auto, a.max_hits, cpu_jobs, a.repeats, a.warmup, flat=flat, ks=ks))
         legs.append(time_leg('%s x %d alternations of literals' % (what, count), texts, make_alternations(np.random.RandomState(2), texts, count, a.alphabet), a.max_hits,
-                             cpu_jobs, a.repeats, a.warmup))
+                             cpu_jobs, a.repeats, a.warmup, ks=ks))
         legs.append(time_leg('%s x %d loops over planted digit runs' % (what, count), texts, make_loops(np.random.RandomState(3), count, a.alphabet), a.max_hits, cpu_jobs,
-                             a.repeats, a.warmup))
-        legs.append(time_leg('%s x 1 never-dying a.*b' % what, texts, make_never_dying(a.alphabet), a.max_hits, min(cpu_jobs, 4), a.repeats, a.warmup))
-    doc = dict(device=torch.cuda.get_device_name(0), alphabet=a.alphabet, repeats=a.repeats, warmup=a.warmup, legs=legs)
+                             a.repeats, a.warmup, ks=ks))
+        legs.append(time_leg('%s x 1 never-dying a.*b' % what, texts, make_never_dying(a.alphabet), a.max_hits, min(cpu_jobs, 4), a.repeats, a.warmup, ks=ks))
+    doc = dict(device=torch.cuda.get_device_name(0), k=list(ks), alphabet=a.alphabet, repeats=a.repeats, warmup=a.warmup, legs=legs)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
         json.dump(doc, f, indent=1)
