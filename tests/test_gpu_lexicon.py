@@ -1,6 +1,8 @@
 """Lexicon correction on the GPU: omp_lexicon_nearest through LexiconMatcher against
 utils/lexicon.py: nearest_cpu, index for index and distance for distance; descriptors the kernel must refuse or clamp; the
-engine's `lexicon=` end to end; one launch against the host computation."""
+engine's `lexicon=` end to end; one launch against the host computation.  Straight through ops.lexicon_nearest: every
+(query length, word length) pair against the definition, slice boundaries, the pool's last bytes, damaged tables between
+canaries, the fill kernel off its tile."""
 import pytest
 import torch
 
@@ -38,6 +40,35 @@ def test_edges(C):
 def test_hostile_descriptors_are_refused_or_clamped(C):
     """q_len of -1 and 200, hi > L, lo < 0 and an inverted range, straight through ops: the documented outputs"""
     _assert_all(C.check_hostile_descriptors())
+
+
+def test_length_grid(C):
+    """query lengths 0 to 64 x word lengths 0 to 255 x six variants (carry chains, two symbols, the whole alphabet, near
+    matches, disjoint alphabets, unknowns), one word per pair: every distance equals the definition under any range_hint,
+    unknown codes match nothing (themselves included), and the distinct queries against the whole grid equal nearest_cpu"""
+    _assert_all(C.check_length_grid())
+
+
+def test_slices(C):
+    """2 queries x 2049 words in 9 slices: equal spellings across a slice boundary and at both ends, the nearest word at the
+    last index, a tie between the last index and index 5, ranges that re-cut the slices"""
+    _assert_all(C.check_slices())
+
+
+def test_pool_tail(C):
+    """pool_bytes = P - 16 .. P with live bytes behind: the cut word answers, nothing at or beyond pool_bytes is used"""
+    _assert_all(C.check_pool_tail())
+
+
+def test_damaged_tables_are_clamped(C):
+    """falling, negative, overlong and 2^31 - 1 offsets, pool_bytes 0 and lowered, a word of 300 characters: answered as
+    the materialised table, canaries round best intact; argument errors leave best untouched"""
+    _assert_all(C.check_damaged_tables())
+
+
+def test_fill_edges(C):
+    """N = 1, 255, 256, 257, 513 into a best full of canary words: empty ranges for all queries, then for the even ones only (the odd ones are answered)"""
+    _assert_all(C.check_fill_edges())
 
 
 def test_engine_lexicon_end_to_end(C):

@@ -1,5 +1,6 @@
 """Lexicon correction, CPU side: the distance (edit_distance_cpu, the definition), the bit-parallel
-specification the kernel is held to on the GPU (nearest_cpu), encoding, ranges, ties, acceptance, the entry point's
+specification the kernel is held to on the GPU (nearest_cpu), the length grid and the damaged tables of the GPU checks
+(their coverage, closed forms and hand-worked clamping), encoding, ranges, ties, acceptance, the entry point's
 arguments against the header, and the routing of `lexicon=` through predict / predict_images / spot_and_recognize with a
 stub matcher."""
 import inspect
@@ -112,6 +113,105 @@ def test_nearest_cpu_distances_equal_edit_distance_cpu():
         bad, total = bad + b, total + n
     assert total >= 20000, total
     assert bad == 0, '%d of %d distances differ' % (bad, total)
+
+
+def test_length_grid_holds_every_pair_and_its_closed_forms():
+    g = K.length_grid_cases()
+    want = K.length_grid_expected()
+    assert len(K.GRID_M) == 12 and len(K.GRID_NW) == 23 and len(K.GRID_VARIANTS) == 6
+    N = len(g['q_len'])
+    assert N == 12 * 23 * 6 == 1656 and g['offsets'].shape == (N + 1,) and g['q_codes'].shape == (N, 64)
+    assert g['pool'].dtype == np.uint8 and g['offsets'].dtype == np.int32 and g['q_len'].dtype == np.int32
+    assert g['offsets'][0] == 0 and g['offsets'][-1] == g['pool'].size == 6 * 12 * sum(K.GRID_NW)
+    seen = sorted(zip(g['m'].tolist(), g['n'].tolist(), g['variant'].tolist()))
+    assert seen == sorted(itertools.product(K.GRID_M, K.GRID_NW, range(6)))
+    assert g['q_len'].tolist() == g['m'].tolist() and np.diff(g['offsets']).tolist() == g['n'].tolist()
+    m, n, v = g['m'], g['n'], g['variant']
+    assert (want[v == 0] == np.abs(m - n)[v == 0]).all()                       # one repeated code
+    assert (want[v == 4] == np.maximum(m, n)[v == 4]).all()                    # no common symbol
+    allu = (v == 5) & ((m + n) % 2 == 0)
+    assert (want[allu] == np.maximum(m, n)[allu]).all()                        # 254 against 255
+    assert (g['closed'][(v == 0) | (v == 4) | allu] >= 0).all() and (g['closed'][~((v == 0) | (v == 4) | allu)] == -1).all()
+    assert (want[g['closed'] >= 0] == g['closed'][g['closed'] >= 0]).all()
+    # the near matches are near: at most two substitutions and the difference in length (m > 0)
+    near = (v == 3) & (m > 0) & (n <= m)
+    assert (want[near] <= (m - n)[near] + 2).all()
+    # the unknown at the column's top bit: the query is the word's head but for its last position, which matches nothing
+    top = (v == 5) & ((m + n) % 2 == 1) & (m <= n) & (m > 0)
+    assert top.sum() > 50 and (want[top] == (n - m)[top] + 1).all()
+    for i in np.nonzero(top)[0][:20]:
+        assert g['q_codes'][i, m[i] - 1] == LX.UNKNOWN_QUERY and g['pool'][g['offsets'][i] + m[i] - 1] == LX.UNKNOWN_WORD
+    assert (want >= np.abs(m - n)).all() and (want <= np.maximum(m, n)).all()
+    u = K.unknown_self_cases()
+    assert len(u['q_len']) == 12 * 23 * 3 and (K.pair_definition(u, 'unknown definition') == u['closed']).all()
+    assert {(int(u['q_codes'][i, 0]), int(u['pool'][u['offsets'][i]])) for i in range(len(u['q_len'])) if u['m'][i] and u['n'][i]} == {
+        (254, 254), (255, 255), (255, 254)}
+
+
+def test_nearest_cpu_equals_the_definition_on_the_length_grid():
+    """the Myers specification against the definition on every pair of the grid, word lengths 0 and 65 .. 255 included, and
+    on whole queries and words of one unknown code"""
+    for g, key in ((K.length_grid_cases(), 'grid definition'), (K.unknown_self_cases(), 'unknown definition')):
+        N = len(g['q_len'])
+        idx, dist = LX.nearest_encoded_cpu(g['q_codes'], g['q_len'], g['pool'], g['offsets'], ranges=[(w, w + 1) for w in range(N)])
+        want = K.pair_definition(g, key)
+        bad = np.nonzero(dist != want)[0]
+        assert not bad.size, 'pair %d (m %d, n %d, variant %d): %d, the definition gives %d' % (
+            bad[0], g['m'][bad[0]], g['n'][bad[0]], g['variant'][bad[0]], dist[bad[0]], want[bad[0]])
+        assert idx.tolist() == list(range(N))
+
+
+def test_materialise():
+    pool = np.arange(10, 30, dtype=np.uint8)                           # 20 bytes
+    clean = np.asarray([0, 3, 3, 9, 20], dtype=np.int32)               # words of 3, 0, 6 and 11 bytes
+    p, o = K.materialise(pool, clean, 20)
+    assert p.dtype == np.uint8 and o.dtype == np.int32 and p.tolist() == pool.tolist() and o.tolist() == clean.tolist()
+    # a falling offset: word 1 runs from 9 to max(3, 9) = 9 and is empty, word 2 from 3 to 12
+    p, o = K.materialise(pool, np.asarray([0, 9, 3, 12, 20], dtype=np.int32), 20)
+    assert o.tolist() == [0, 9, 9, 18, 26] and p.tolist() == list(range(10, 19)) + list(range(13, 22)) + list(range(22, 30))
+    # a negative offset starts at 0: word 1 is pool[0:9], word 0 is pool[0:max(-5, 0)] and empty
+    p, o = K.materialise(pool, np.asarray([0, -5, 9, 9, 20], dtype=np.int32), 20)
+    assert o.tolist() == [0, 0, 9, 9, 20] and p.tolist() == list(range(10, 19)) + list(range(19, 30))
+    # overlong: offsets past pool_bytes = 12 are cut there; a start past it gives an empty word at 12
+    p, o = K.materialise(pool, np.asarray([0, 3, 15, 18, 20], dtype=np.int32), 12)
+    assert o.tolist() == [0, 3, 12, 12, 12] and p.tolist() == list(range(10, 22))
+    # 2^31 - 1: word 1 runs to the pool's end, word 2 starts at the clamped 20 and is empty, word 3 is pool[9:20] as before
+    p, o = K.materialise(pool, np.asarray([0, 3, 2 ** 31 - 1, 9, 20], dtype=np.int32), 20)
+    assert o.tolist() == [0, 3, 20, 20, 31] and p.tolist() == pool.tolist() + list(range(19, 30))
+    # pool_bytes 0: every word is empty
+    p, o = K.materialise(pool, clean, 0)
+    assert o.tolist() == [0, 0, 0, 0, 0] and p.size == 0 and p.dtype == np.uint8
+    # a word of 300 is cut at 255
+    long_pool = (np.arange(310) % 251).astype(np.uint8)
+    p, o = K.materialise(long_pool, np.asarray([0, 5, 305, 310], dtype=np.int32), 310)
+    assert o.tolist() == [0, 5, 260, 265] and p.tolist() == long_pool[:260].tolist() + long_pool[305:].tolist()
+    # the specification applies to the result
+    idx, dist = LX.nearest_encoded_cpu(np.zeros((1, 64), dtype=np.uint8), np.zeros(1, dtype=np.int32), *K.materialise(long_pool, np.asarray([0, 300, 310]), 310))
+    assert (idx.tolist(), dist.tolist()) == ([1], [10])
+
+
+def test_device_case_builders():
+    """the operands of the pool-tail and damaged-table checks are what their docstrings say"""
+    words, queries = K.pool_tail_case()
+    assert len(words) == 40 and [len(w) for w in words[-3:]] == [15, 14, 15] and all(1 <= len(w) <= 15 for w in words)
+    assert queries[:3] == [words[39], words[38], words[37]] and not set(words[39]) & set(c for w in words[:39] for c in w)
+    pool, offsets, codes, q_len = K._pack_codes(words, queries)
+    P = int(pool.size)
+    for pb in range(P - 16, P + 1):                                    # the cut word answers its own spelling while it is not empty
+        idx, dist = LX.nearest_encoded_cpu(codes, q_len, *K.materialise(pool, offsets, pb))
+        k = max(15 - (P - pb), 0)
+        assert dist[0] == 15 - k and (idx[0] == 39 if k else idx[0] < 39)
+    pool, offsets, L, codes, q_len, cases = K.damaged_table_cases()
+    assert L == 300 and offsets[101] - offsets[100] == 300 and len(cases) == 6
+    with pytest.raises(ValueError):
+        LX.encode_words(['x' * 300], DEFAULT_CHARS)
+    for name, off, pb, ranges in cases:
+        p, o = K.materialise(pool, off, pb)
+        n = np.diff(o)
+        assert o.size == L + 1 and n.min() >= 0 and n.max() <= 255 and o[-1] == p.size, name
+    falling = cases[0][1]
+    assert (np.diff(falling.astype(np.int64)) < 0).sum() > 30 and falling.min() < 0
+    assert cases[1][1].max() > cases[1][2] and cases[2][1].max() == 2 ** 31 - 1 and cases[3][2] == 0
 
 
 def test_case_folding_and_unknown_characters():
