@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libomp355.so')
-SOURCES = ['api.hip', 'gemm.hip', 'gemm256.hip', 'gemm4w.hip', 'gemm4wr.hip', 'gemm4wp.hip', 'mlp.hip', 'norm.hip', 'swin_attn.hip', 'swin_block.hip', 'fpn.hip', 'decoder.hip', 'dec_rows.hip', 'kv_rows.hip', 'vit.hip', 'preprocess.hip', 'word_crop.hip', 'lexicon.hip', 'lexicon_post.hip', 'window_points.hip', 'overlap.hip', 'score.hip', 'reading.hip', 'tiles.hip', 'page_text.hip', 'page_search.hip', 'page_align.hip', 'page_pattern.hip', 'page_regex.hip', 'page_regex_fuzzy.hip']
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(CSRC, 'swin_common.h'), os.path.join(CSRC, 'myers.h'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
+SOURCES = ['api.hip', 'gemm.hip', 'gemm256.hip', 'gemm4w.hip', 'gemm4wr.hip', 'gemm4wp.hip', 'mlp.hip', 'norm.hip', 'swin_attn.hip', 'swin_block.hip', 'fpn.hip', 'decoder.hip', 'dec_rows.hip', 'kv_rows.hip', 'vit.hip', 'preprocess.hip', 'word_crop.hip', 'lexicon.hip', 'lexicon_post.hip', 'window_points.hip', 'overlap.hip', 'score.hip', 'reading.hip', 'tiles.hip', 'page_text.hip', 'page_search.hip', 'page_align.hip', 'page_pattern.hip', 'page_regex.hip']
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'omp355_debug.h'), os.path.join(CSRC, 'gemm_common.h'), os.path.join(CSRC, 'rows_common.inc'), os.path.join(CSRC, 'swin_common.h'), os.path.join(CSRC, 'myers.h'), os.path.join(CSRC, 'page_frame.h'), os.path.join(os.path.dirname(HERE), 'include', 'omp355.h')]
 # the units that hold gemm_4w* kernels and the row-owner kernels: their device assembly stays next to the object, the audits read it
 AUDITED = ('gemm4w.hip', 'gemm4wr.hip', 'gemm4wp.hip', 'dec_rows.hip', 'kv_rows.hip')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']

@@ -4,7 +4,7 @@
 // D[i][j] = min(D[i-1][j-1] + (t_j not in C_i), D[i-1][j] + skip_i, D[i][j-1] + 1), skip_i = 0 for an optional position, else 1;
 // v_j = min(D[P][j], k + 1).
 //
-// The frame is page_search.hip's; only the column step differs:
+// The job frame is page_frame.h's (pg_window), which page_search.hip shares; PpStep holds the column:
 //
 //   page_pattern_kernel   one wave (a 64-thread workgroup) per job (page, pattern).
 //     rows      Wu and Manber's R_0 .. R_k (1992), one 64-bit word each, in registers: bit i of R_d says that a prefix of i + 1 positions
@@ -34,28 +34,14 @@
 // A job out of range (a page or pattern that is not there, P outside 1 .. 64, opt bits at or above P, no mandatory position, k outside
 // 0 .. min(Mand - 1, 8), a page above 65535 characters, a range outside the pool) is REFUSED on the device: n_hits = -1, best and hits -1,
 // and nothing outside the pool is read.  Nothing is allocated and nothing synchronises.
-#include "common.h"
+#include "page_frame.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int PP_LEN_MAX = 65535;      // characters a page
-constexpr int PP_POS_MAX = 64;         // positions a pattern
 constexpr int PP_K_MAX = 8;            // errors at the most
-constexpr int PP_CHUNK = 128;          // end columns per lane
-constexpr int PP_HITS_MAX = 64;        // hits kept per job
-constexpr int PP_SIGMA_MAX = 254;
-constexpr int PP_JOBS_MAX = 1 << 20;
-constexpr int PP_ROUND = 64 * PP_CHUNK;                    // end columns per round of the wave
-constexpr int PP_BEFORE = 128;                             // characters staged before the round's first chunk
-constexpr int PP_STAGE = PP_BEFORE + PP_ROUND + 1;         // characters staged per round
-constexpr int PP_TEXT_BYTES = PP_STAGE + 4 * (PP_STAGE / PP_CHUNK + 1);
+constexpr int PP_BEFORE = 128;         // characters staged before the round's first chunk
 
-static_assert(PP_BEFORE >= PP_POS_MAX + PP_K_MAX && PP_TEXT_BYTES >= PP_STAGE + 4 * ((PP_STAGE - 1) / PP_CHUNK) && PP_HITS_MAX <= 64, "page_pattern layout");
-
-// where staged character `rel` (0 = PP_BEFORE characters before the round's first chunk) lives in LDS
-__device__ __forceinline__ int pp_at(int rel) { return rel + 4 * (rel / PP_CHUNK); }
+static_assert(PP_BEFORE >= PG_POS_MAX + PP_K_MAX, "page_pattern layout");
 
 // the words of the closure over the optional positions `opt`
 struct Closure {
@@ -109,91 +95,47 @@ __device__ __forceinline__ int pp_value(const u64 (&R)[K], int top) {
   return v;
 }
 
-// The body of one job under k = K - 1, by the whole wave -> hits of all rounds; *key_out this lane's best key
+// pg_window's Stepper under k = K - 1: the rows of one lane
+template <int K>
+struct PpStep {
+  int P, top;
+  Closure cl, rcl;                                         // of the pattern, and of the reversed pattern for the start walk
+  u64 R[K];
+  __device__ __forceinline__ PpStep(int P_, u64 opt) : P(P_), top(P_ - 1), cl(opt), rcl(__brevll(opt) >> (64 - P_)) {}
+  __device__ __forceinline__ int warm() const { return P + K - 1; }
+  __device__ __forceinline__ int stage_from() const { return 0; }
+  __device__ __forceinline__ int none() const { return K; }   // k + 1: nothing within k
+  __device__ __forceinline__ int tol() const { return K - 1; }
+  __device__ __forceinline__ void fresh() { pp_fresh<K>(R, cl); }
+  __device__ __forceinline__ int step(u64 B, int) {
+    pp_step<K, true>(R, B, cl, 1ull);
+    return pp_value<K>(R, top);
+  }
+  // the anchored rows of the reversed pattern over all min(end, P + dist) characters: the LAST l whose R_dist holds bit P - 1
+  template <class At>
+  __device__ __forceinline__ int start(int end, int dist, At at) const {
+    u64 Q[K];
+    pp_fresh<K>(Q, rcl);
+    const int lmax = min(end, P + dist);
+    int found = 0;
+    for (int l = 1; l <= lmax; ++l) {
+      const u64 B = __brevll(at(end - l)) >> (64 - P);
+      pp_step<K, false>(Q, B, rcl, l == 1 ? 1ull : 0ull);
+      u64 hit = 0;
+#pragma unroll
+      for (int d = 0; d < K; ++d)
+        if (d == dist) hit = Q[d];
+      if ((hit >> top) & 1ull) found = l;                  // the anchored cost is never below dist: the bit says it equals dist
+    }
+    return found ? end - found : -2;                       // -2 cannot happen: the start exists within P + dist characters
+  }
+};
+
 template <int K>
 __device__ __forceinline__ int pp_job(const uint8_t* __restrict__ t, int n, int P, u64 opt, int sigma, int H, const u64* mask, uint8_t* text, int2* slot,
                                       int2* list, int32_t* jhits, u64* key_out) {
-  const int lane = threadIdx.x;
-  const int k = K - 1, top = P - 1, W = P + k;
-  const Closure cl(opt);
-  const Closure rcl(__brevll(opt) >> (64 - P));
-  u64 key = ((u64)K << 32);                                // (k + 1, 0): nothing within k
-  int base = 0;                                            // hits of the rounds before this one
-  for (int r0 = 0; r0 < n; r0 += PP_ROUND) {
-    // ---- stage t[r0 - PP_BEFORE .. r0 + PP_ROUND] ----
-    const int hi = min(PP_STAGE, n - r0 + PP_BEFORE);      // staged characters that exist
-    for (int rel = lane; rel < hi; rel += 64) {
-      const int pos = r0 - PP_BEFORE + rel;
-      if (pos >= 0) text[pp_at(rel)] = t[pos];
-    }
-    __syncthreads();
-    // ---- the lanes walk their chunks in step ----
-    const int cs = r0 + lane * PP_CHUNK;
-    u64 R[K];
-    pp_fresh<K>(R, cl);
-    int s0 = K, s1 = K, s2 = K;                            // v_j, v_{j-1}, v_{j-2}
-    int cnt = 0;
-    const int imax = min(PP_CHUNK + 1, n - r0 + 1);        // lane 0 has the most columns left
-    // the class word of column j, one column ahead of the recurrence: the two LDS reads do not depend on it
-    auto class_of = [&](int j) -> u64 { return (j >= 1 && j <= n) ? mask[min((int)text[pp_at(j - 1 - r0 + PP_BEFORE)], sigma)] : 0ull; };
-    u64 bn = class_of(cs + 1 - W);
-    for (int i = 1 - W; i <= imax; ++i) {
-      const int j = cs + i;
-      const u64 B = bn;
-      bn = i < imax ? class_of(j + 1) : 0ull;
-      s2 = s1;
-      s1 = s0;
-      if (j >= 1 && j <= n) {
-        pp_step<K, true>(R, B, cl, 1ull);
-        s0 = pp_value<K>(R, top);
-      }
-      const int e = j - 1;                                 // the column that can be judged now
-      if (i >= 2 && e <= n) {                              // e is one of this lane's own columns
-        const u64 ke = ((u64)s1 << 32) | (u64)e;
-        if (ke < key) key = ke;
-        if (s1 <= k && s1 <= s2 && (e == n || s1 < s0)) {
-          if (cnt < H) list[cnt] = make_int2(e, s1);
-          ++cnt;
-        }
-      }
-    }
-    // ---- the exclusive scan of the counts over the lanes ----
-    int incl = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    const int total = __shfl(incl, 63, 64);
-    const int first = base + incl - cnt;
-    for (int i = 0; i < cnt && first + i < H; ++i) slot[first + i] = list[i];   // a lane reads back what it wrote itself
-    __syncthreads();
-    const int filled = min(base + total, H);
-    if (lane >= base && lane < filled) {
-      // ---- the start of hit `lane`: the anchored rows of the reversed pattern ----
-      const int end = slot[lane].x, dist = slot[lane].y;
-      u64 Q[K];
-      pp_fresh<K>(Q, rcl);
-      const int lmax = min(end, P + dist);
-      int found = 0;
-      for (int l = 1; l <= lmax; ++l) {
-        const int c = text[pp_at(end - l - r0 + PP_BEFORE)];
-        const u64 B = __brevll(mask[min(c, sigma)]) >> (64 - P);
-        pp_step<K, false>(Q, B, rcl, l == 1 ? 1ull : 0ull);
-        u64 at = 0;
-#pragma unroll
-        for (int d = 0; d < K; ++d)
-          if (d == dist) at = Q[d];
-        if ((at >> top) & 1ull) found = l;                 // the anchored cost is never below dist: the bit says it equals dist
-      }
-      jhits[3 * lane] = end;
-      jhits[3 * lane + 1] = dist;
-      jhits[3 * lane + 2] = found ? end - found : -2;      // -2 cannot happen: the start exists within P + dist characters
-    }
-    base += total;
-    __syncthreads();                                       // the next round overwrites text and slot
-  }
-  *key_out = key;
-  return base;
+  PpStep<K> st(P, opt);
+  return pg_window<PP_BEFORE>(st, t, n, sigma, H, mask, text, slot, list, jhits, key_out);
 }
 
 __global__ __launch_bounds__(64) void page_pattern_kernel(const uint8_t* __restrict__ pool, int64_t pool_bytes, const int32_t* __restrict__ page_off,
@@ -201,9 +143,9 @@ __global__ __launch_bounds__(64) void page_pattern_kernel(const uint8_t* __restr
                                                           const u64* __restrict__ opts, const int32_t* __restrict__ pat_len,
                                                           const int32_t* __restrict__ tol, int n_patterns, const int32_t* __restrict__ jobs, int sigma, int H,
                                                           int2* scratch, int32_t* __restrict__ best, int32_t* __restrict__ n_hits, int32_t* __restrict__ hits) {
-  __shared__ __align__(16) u64 mask[PP_SIGMA_MAX + 2];
-  __shared__ __align__(16) uint8_t text[PP_TEXT_BYTES];
-  __shared__ int2 slot[PP_HITS_MAX];
+  __shared__ __align__(16) u64 mask[PG_SIGMA_MAX + 2];
+  __shared__ __align__(16) uint8_t text[PgText<PP_BEFORE>::BYTES];
+  __shared__ int2 slot[PG_HITS_MAX];
   const int job = blockIdx.x, lane = threadIdx.x;
   int32_t* jhits = hits + (int64_t)job * H * 3;
   const int p = jobs[2 * job], qi = jobs[2 * job + 1];
@@ -218,24 +160,17 @@ __global__ __launch_bounds__(64) void page_pattern_kernel(const uint8_t* __restr
     P = pat_len[qi];
     opt = opts[qi];
     k = tol[qi];
-    ok = n >= 0 && n <= PP_LEN_MAX && P >= 1 && P <= PP_POS_MAX && po >= 0 && po + n <= pool_bytes;
+    ok = n >= 0 && n <= PG_LEN_MAX && P >= 1 && P <= PG_POS_MAX && po >= 0 && po + n <= pool_bytes;
     if (ok) {
       const int mand = P - __popcll(opt);
       ok = (P == 64 || (opt >> P) == 0) && mand >= 1 && k >= 0 && k <= min(mand - 1, PP_K_MAX);
     }
   }
   if (!ok) {
-    if (lane == 0) {
-      n_hits[job] = -1;
-      best[2 * job] = -1;
-      best[2 * job + 1] = -1;
-    }
-    for (int i = lane; i < 3 * H; i += 64) jhits[i] = -1;
+    pg_refuse(job, H, best, n_hits, jhits);
     return;
   }
-  const u64* __restrict__ row = masks + (int64_t)qi * (sigma + 1);
-  for (int c = lane; c < sigma; c += 64) mask[c] = row[c];
-  if (lane == 0) mask[sigma] = 0;                          // whatever the table holds there: a code at or above sigma is in no class
+  pg_classes(mask, masks, qi, sigma);
   __syncthreads();
   const uint8_t* __restrict__ t = pool + po;
   int2* list = scratch + ((int64_t)job * 64 + lane) * H;   // this lane's first H hits of the round: (end, dist)
@@ -252,11 +187,7 @@ __global__ __launch_bounds__(64) void page_pattern_kernel(const uint8_t* __restr
     case 7: base = pp_job<8>(t, n, P, opt, sigma, H, mask, text, slot, list, jhits, &key); break;
     default: base = pp_job<9>(t, n, P, opt, sigma, H, mask, text, slot, list, jhits, &key); break;
   }
-  for (int g = min(base, H) + lane; g < H; g += 64) {
-    jhits[3 * g] = -1;
-    jhits[3 * g + 1] = -1;
-    jhits[3 * g + 2] = -1;
-  }
+  pg_tail(jhits, base, H);
   for (int d = 32; d >= 1; d >>= 1) {
     const u64 other = __shfl_xor(key, d, 64);
     if (other < key) key = other;
@@ -276,11 +207,7 @@ extern "C" int omp_page_pattern_search(const uint8_t* pool, int64_t pool_bytes, 
                                        int32_t* n_hits, int32_t* hits, omp_stream_t s) {
   OMP_CHECK_ARG(pool && page_off && page_len && masks && opt && pat_len && k && jobs && scratch && best && n_hits && hits,
                 "omp_page_pattern_search: null pointer");
-  OMP_CHECK_ARG(n_jobs > 0 && n_jobs <= PP_JOBS_MAX && n_pages > 0 && n_patterns > 0 && pool_bytes >= 0 && pool_bytes <= 0x7fffffffll,
-                "omp_page_pattern_search: %d jobs (1 .. %d), %d pages, %d patterns, %lld pool bytes", n_jobs, PP_JOBS_MAX, n_pages, n_patterns,
-                (long long)pool_bytes);
-  OMP_CHECK_ARG(sigma >= 0 && sigma <= PP_SIGMA_MAX, "omp_page_pattern_search: sigma %d (0 .. %d)", sigma, PP_SIGMA_MAX);
-  OMP_CHECK_ARG(max_hits >= 1 && max_hits <= PP_HITS_MAX, "omp_page_pattern_search: max_hits %d (1 .. %d)", max_hits, PP_HITS_MAX);
+  if (const int rc = pg_check_args("omp_page_pattern_search", "patterns", n_jobs, n_pages, n_patterns, pool_bytes, sigma, max_hits)) return rc;
   const int64_t need = (int64_t)n_jobs * 64 * max_hits * (int64_t)sizeof(int2);
   OMP_CHECK_ARG(scratch_bytes >= need, "omp_page_pattern_search: %lld bytes of scratch, %d jobs at max_hits %d need %lld", (long long)scratch_bytes,
                 n_jobs, max_hits, (long long)need);

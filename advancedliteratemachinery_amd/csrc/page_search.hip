@@ -4,7 +4,8 @@
 //
 // A query has at most 64 characters, so Myers' bit-parallel column (1999) is ONE 64-bit word and one lane runs it by itself:
 //
-//   page_search_kernel   one wave (a 64-thread workgroup) per job (page, query).
+//   page_search_kernel   one wave (a 64-thread workgroup) per job (page, query).  The job frame -- the round loop, the hit lists, the slot
+//                        scan, the refusal -- is page_frame.h's (pg_window), which page_pattern.hip shares; PsStep is the column.
 //     chunks    lane l owns the end columns cs + 1 .. cs + 128 of the text, cs = 128 (64 r + l) in round r; a page of up to 65535
 //               characters takes up to 8 rounds.  A lane starts 2m columns before cs with a fresh column (Pv all ones, score m):
 //               every alignment of cost <= m covers at most 2m characters, so v_cs and every later score equal those of the whole
@@ -27,34 +28,53 @@
 // the pool, k outside 0 .. m - 1) is REFUSED on the device: n_hits = -1, best and hits -1, and nothing outside the pool is read.
 // Nothing is allocated and nothing synchronises: pool, tables, scratch and outputs are the caller's.
 #include "myers.h"
+#include "page_frame.h"
 
 namespace {
 
-constexpr int PS_LEN_MAX = 65535;      // characters a page
 constexpr int PS_QUERY_MAX = 64;       // characters a query
-constexpr int PS_CHUNK = 128;          // end columns per lane
-constexpr int PS_HITS_MAX = 64;        // hits kept per job
-constexpr int PS_SIGMA_MAX = 254;
 constexpr int PS_NONE = 255;           // the code that equals nothing
-constexpr int PS_JOBS_MAX = 1 << 20;
-constexpr int PS_ROUND = 64 * PS_CHUNK;                    // end columns per round of the wave
 constexpr int PS_BEFORE = 2 * PS_QUERY_MAX;                // characters staged before the round's first chunk
-constexpr int PS_STAGE = PS_BEFORE + PS_ROUND + 1;         // characters staged per round
-constexpr int PS_TEXT_BYTES = PS_STAGE + 4 * (PS_STAGE / PS_CHUNK + 1);
 
-static_assert(PS_BEFORE >= 2 * PS_QUERY_MAX && PS_TEXT_BYTES >= PS_STAGE + 4 * ((PS_STAGE - 1) / PS_CHUNK) && PS_HITS_MAX <= 64, "page_search layout");
+static_assert(PS_QUERY_MAX == PG_POS_MAX, "page_search layout");
 
-// where staged character `rel` (0 = PS_BEFORE characters before the round's first chunk) lives in LDS
-__device__ __forceinline__ int ps_at(int rel) { return rel + 4 * (rel / PS_CHUNK); }
+// pg_window's Stepper: Myers' column of one lane.  Only the 2m characters of the warm-up are staged before a round's first chunk
+// (PS_BEFORE - W): nothing earlier is read.
+struct PsStep {
+  int m, k, top;
+  u64 Pv, Mv;
+  __device__ __forceinline__ int warm() const { return 2 * m; }
+  __device__ __forceinline__ int stage_from() const { return PS_BEFORE - 2 * m; }
+  __device__ __forceinline__ int none() const { return m; }
+  __device__ __forceinline__ int tol() const { return k; }
+  __device__ __forceinline__ void fresh() {
+    Pv = ~0ull;
+    Mv = 0;
+  }
+  __device__ __forceinline__ int step(u64 eq, int v) { return v + myers_step(eq, Pv, Mv, top, 0); }
+  // the anchored reverse recurrence to the FIRST l whose score equals dist, at most m + dist <= 127 characters
+  template <class At>
+  __device__ __forceinline__ int start(int end, int dist, At at) const {
+    u64 rPv = ~0ull, rMv = 0;
+    int score = m, l = 0;
+    const int lmax = min(end, m + dist);
+    while (score != dist && l < lmax) {
+      ++l;
+      const u64 Eq = __brevll(at(end - l)) >> (64 - m);
+      score += myers_step(Eq, rPv, rMv, top, 1);
+    }
+    return score == dist ? end - l : -2;                   // -2 cannot happen: the start exists within m + dist characters
+  }
+};
 
 __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restrict__ pool, int64_t pool_bytes, const int32_t* __restrict__ page_off,
                                                          const int32_t* __restrict__ page_len, int n_pages, const int32_t* __restrict__ query_off,
                                                          const int32_t* __restrict__ query_len, const int32_t* __restrict__ tol, int n_queries,
                                                          const int32_t* __restrict__ jobs, int sigma, int H, int2* scratch,
                                                          int32_t* __restrict__ best, int32_t* __restrict__ n_hits, int32_t* __restrict__ hits) {
-  __shared__ __align__(16) u64 peq[PS_SIGMA_MAX + 2];
-  __shared__ __align__(16) uint8_t text[PS_TEXT_BYTES];
-  __shared__ int2 slot[PS_HITS_MAX];
+  __shared__ __align__(16) u64 peq[PG_SIGMA_MAX + 2];
+  __shared__ __align__(16) uint8_t text[PgText<PS_BEFORE>::BYTES];
+  __shared__ int2 slot[PG_HITS_MAX];
   const int job = blockIdx.x, lane = threadIdx.x;
   int32_t* jhits = hits + (int64_t)job * H * 3;
   const int p = jobs[2 * job], qi = jobs[2 * job + 1];
@@ -68,19 +88,12 @@ __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restri
     m = query_len[qi];
     qo = query_off[qi];
     k = tol[qi];
-    ok = n >= 0 && n <= PS_LEN_MAX && m >= 1 && m <= PS_QUERY_MAX && po >= 0 && qo >= 0 && po + n <= pool_bytes && qo + m <= pool_bytes && k >= 0 && k < m;
+    ok = n >= 0 && n <= PG_LEN_MAX && m >= 1 && m <= PS_QUERY_MAX && po >= 0 && qo >= 0 && po + n <= pool_bytes && qo + m <= pool_bytes && k >= 0 && k < m;
   }
   if (!ok) {
-    if (lane == 0) {
-      n_hits[job] = -1;
-      best[2 * job] = -1;
-      best[2 * job + 1] = -1;
-    }
-    for (int i = lane; i < 3 * H; i += 64) jhits[i] = -1;
+    pg_refuse(job, H, best, n_hits, jhits);
     return;
   }
-  const uint8_t* __restrict__ t = pool + po;
-  const int top = m - 1;
   // ---- Peq: one ballot per query character ----
   for (int c = lane; c <= sigma; c += 64) peq[c] = 0;
   const int qc = lane < m ? (int)pool[qo + lane] : PS_NONE;
@@ -92,78 +105,10 @@ __global__ __launch_bounds__(64) void page_search_kernel(const uint8_t* __restri
   }
   __syncthreads();
   int2* list = scratch + ((int64_t)job * 64 + lane) * H;   // this lane's first H hits of the round: (end, dist)
-  u64 key = ((u64)m << 32);                                // (m, 0): the empty match
-  int base = 0;                                            // hits of the rounds before this one
-  const int W = 2 * m;
-  for (int r0 = 0; r0 < n; r0 += PS_ROUND) {
-    // ---- stage t[r0 - PS_BEFORE .. r0 + PS_ROUND] ----
-    const int hi = min(PS_STAGE, n - r0 + PS_BEFORE);      // staged characters that exist
-    for (int rel = PS_BEFORE - W + lane; rel < hi; rel += 64) {
-      const int pos = r0 - PS_BEFORE + rel;
-      if (pos >= 0) text[ps_at(rel)] = t[pos];
-    }
-    __syncthreads();
-    // ---- the lanes walk their chunks in step ----
-    const int cs = r0 + lane * PS_CHUNK;
-    u64 Pv = ~0ull, Mv = 0;
-    int s0 = m, s1 = m, s2 = m;                            // v_j, v_{j-1}, v_{j-2}
-    int cnt = 0;
-    const int imax = min(PS_CHUNK + 1, n - r0 + 1);        // lane 0 has the most columns left
-    // the Eq word of column j, one column ahead of the recurrence: the two LDS reads do not depend on it
-    auto eq_of = [&](int j) -> u64 { return (j >= 1 && j <= n) ? peq[min((int)text[ps_at(j - 1 - r0 + PS_BEFORE)], sigma)] : 0ull; };
-    u64 eqn = eq_of(cs + 1 - W);
-    for (int i = 1 - W; i <= imax; ++i) {
-      const int j = cs + i;
-      const u64 eq = eqn;
-      eqn = i < imax ? eq_of(j + 1) : 0ull;
-      s2 = s1;
-      s1 = s0;
-      if (j >= 1 && j <= n) s0 += myers_step(eq, Pv, Mv, top, 0);
-      const int e = j - 1;                                 // the column that can be judged now
-      if (i >= 2 && e <= n) {                              // e is one of this lane's own columns
-        const u64 ke = ((u64)s1 << 32) | (u64)e;
-        if (ke < key) key = ke;
-        if (s1 <= k && s1 <= s2 && (e == n || s1 < s0)) {
-          if (cnt < H) list[cnt] = make_int2(e, s1);
-          ++cnt;
-        }
-      }
-    }
-    // ---- the exclusive scan of the counts over the lanes ----
-    int incl = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    const int total = __shfl(incl, 63, 64);
-    const int first = base + incl - cnt;
-    for (int i = 0; i < cnt && first + i < H; ++i) slot[first + i] = list[i];   // a lane reads back what it wrote itself
-    __syncthreads();
-    const int filled = min(base + total, H);
-    if (lane >= base && lane < filled) {
-      // ---- the start of hit `lane`: the anchored reverse recurrence ----
-      const int end = slot[lane].x, dist = slot[lane].y;
-      u64 rPv = ~0ull, rMv = 0;
-      int score = m, l = 0;
-      const int lmax = min(end, m + dist);
-      while (score != dist && l < lmax) {
-        ++l;
-        const int c = text[ps_at(end - l - r0 + PS_BEFORE)];
-        const u64 Eq = __brevll(peq[min(c, sigma)]) >> (64 - m);
-        score += myers_step(Eq, rPv, rMv, top, 1);
-      }
-      jhits[3 * lane] = end;
-      jhits[3 * lane + 1] = dist;
-      jhits[3 * lane + 2] = score == dist ? end - l : -2;   // -2 cannot happen: the start exists within m + dist characters
-    }
-    base += total;
-    __syncthreads();                                       // the next round overwrites text and slot
-  }
-  for (int g = min(base, H) + lane; g < H; g += 64) {
-    jhits[3 * g] = -1;
-    jhits[3 * g + 1] = -1;
-    jhits[3 * g + 2] = -1;
-  }
+  PsStep st{m, k, m - 1, 0, 0};
+  u64 key;                                                 // from (m, 0): the empty match
+  const int base = pg_window<PS_BEFORE>(st, pool + po, n, sigma, H, peq, text, slot, list, jhits, &key);
+  pg_tail(jhits, base, H);
   for (int d = 32; d >= 1; d >>= 1) {
     const u64 other = __shfl_xor(key, d, 64);
     if (other < key) key = other;
@@ -182,10 +127,7 @@ extern "C" int omp_page_search(const uint8_t* pool, int64_t pool_bytes, const in
                                int n_jobs, int sigma, int max_hits, void* scratch, int64_t scratch_bytes, int32_t* best, int32_t* n_hits,
                                int32_t* hits, omp_stream_t s) {
   OMP_CHECK_ARG(pool && page_off && page_len && query_off && query_len && k && jobs && scratch && best && n_hits && hits, "omp_page_search: null pointer");
-  OMP_CHECK_ARG(n_jobs > 0 && n_jobs <= PS_JOBS_MAX && n_pages > 0 && n_queries > 0 && pool_bytes >= 0 && pool_bytes <= 0x7fffffffll,
-                "omp_page_search: %d jobs (1 .. %d), %d pages, %d queries, %lld pool bytes", n_jobs, PS_JOBS_MAX, n_pages, n_queries, (long long)pool_bytes);
-  OMP_CHECK_ARG(sigma >= 0 && sigma <= PS_SIGMA_MAX, "omp_page_search: sigma %d (0 .. %d)", sigma, PS_SIGMA_MAX);
-  OMP_CHECK_ARG(max_hits >= 1 && max_hits <= PS_HITS_MAX, "omp_page_search: max_hits %d (1 .. %d)", max_hits, PS_HITS_MAX);
+  if (const int rc = pg_check_args("omp_page_search", "queries", n_jobs, n_pages, n_queries, pool_bytes, sigma, max_hits)) return rc;
   const int64_t need = (int64_t)n_jobs * 64 * max_hits * (int64_t)sizeof(int2);
   OMP_CHECK_ARG(scratch_bytes >= need, "omp_page_search: %lld bytes of scratch, %d jobs at max_hits %d need %lld", (long long)scratch_bytes, n_jobs,
                 max_hits, (long long)need);

@@ -1,7 +1,7 @@
 """Page search on records: where a phrase (find_text: DESIGN.md section 25, utils/page_search.py, csrc/page_search.hip) or a shape such as a
 date, an amount or an id (find_pattern: DESIGN.md section 29, utils/page_pattern.py, csrc/page_pattern.hip; find_regex: the same with
 groups, alternation and real loops, exactly: DESIGN.md section 30, utils/page_regex.py, csrc/page_regex.hip; with max_dist or max_ratio
-within up to 4 errors: section 31, csrc/page_regex_fuzzy.hip) stands on a read page, which words carry it and how badly it was misread."""
+within up to 4 errors: section 31, the same unit) stands on a read page, which words carry it and how badly it was misread."""
 import numpy as np
 
 
@@ -38,6 +38,39 @@ def _carried(recs, text, w_start, w_end, rows):
         carried = recs[first:last + 1]
         hits.append(dict(dist=d, chars=(s, e), text=text[s:e], words=(first, last), records=carried, box=_box(carried)))
     return hits, dropped
+
+
+def _shape_jobs(records, shapes, caller, plural, a_shape, field, sep, normalise, parse):
+    """what find_pattern and find_regex share: the record check, one list of shapes per image (a tuple is a (name, string) pair, so
+    per-image lists are LISTS), the (name, string) unpacking, and the table of distinct strings, each parsed once by `parse` in the order
+    they first occur -> (records as lists, pages = page_index per image, parsed, jobs = [(image, shape)], named = [(name, string)] per
+    job)"""
+    from ..utils.page_search import page_index
+    records = [list(recs) for recs in records]
+    for b, recs in enumerate(records):
+        for r in recs:
+            if not isinstance(r, dict) or 'polys' not in r:
+                raise ValueError('image %d: %s needs text-spotting records (dicts with `polys`)' % (b, caller))
+    shapes = list(shapes)
+    if shapes and all(isinstance(p, list) for p in shapes):
+        if len(shapes) != len(records):
+            raise ValueError('%s holds %d lists for %d images' % (plural, len(shapes), len(records)))
+        lists = [list(p) for p in shapes]
+    else:
+        lists = [shapes] * len(records)
+    pages = [page_index(recs, field, sep, normalise) for recs in records]
+    table, parsed, jobs, named = {}, [], [], []
+    for b, ps in enumerate(lists):
+        for p in ps:
+            name, src = (None, p) if isinstance(p, str) else p if isinstance(p, tuple) and len(p) == 2 else (None, None)
+            if not isinstance(src, str) or not (name is None or isinstance(name, str)):
+                raise ValueError('%s is a string or a (name, string) pair, got %r' % (a_shape, p))
+            if src not in table:
+                table[src] = len(table)
+                parsed.append(parse(src))
+            jobs.append((b, table[src]))
+            named.append((name, src))
+    return records, pages, parsed, jobs, named
 
 
 def find_text(records, queries, field='rec', max_dist=None, max_ratio=0.2, sep=' ', normalise=str.casefold, max_hits=16, searcher=None,
@@ -107,32 +140,13 @@ def find_pattern(records, patterns, field='rec', max_dist=None, max_ratio=0.0, s
     (dist, chars, text, words, records, box), with one difference: chars starts at the LEAST start that attains dist, the longest match
     (`\\d{1,4}` in `12345` is `2345`, not `5`), where find_text reports the shortest.  A hit that touches no word is dropped and counted."""
     from ..utils import page_pattern as PP
-    from ..utils.page_search import page_index
-    records = [list(recs) for recs in records]
-    for b, recs in enumerate(records):
-        for r in recs:
-            if not isinstance(r, dict) or 'polys' not in r:
-                raise ValueError('image %d: find_pattern needs text-spotting records (dicts with `polys`)' % b)
-    patterns = list(patterns)
-    if patterns and all(isinstance(p, list) for p in patterns):            # a tuple is a (name, string) pair, so per-image lists are LISTS
-        if len(patterns) != len(records):
-            raise ValueError('patterns holds %d lists for %d images' % (len(patterns), len(records)))
-        lists = [list(p) for p in patterns]
-    else:
-        lists = [patterns] * len(records)
-    pages = [page_index(recs, field, sep, normalise) for recs in records]
-    table, parsed, k, jobs, named = {}, [], [], [], []
-    for b, ps in enumerate(lists):
-        for p in ps:
-            name, src = (None, p) if isinstance(p, str) else p if isinstance(p, tuple) and len(p) == 2 else (None, None)
-            if not isinstance(src, str) or not (name is None or isinstance(name, str)):
-                raise ValueError('a pattern is a string or a (name, string) pair, got %r' % (p,))
-            if src not in table:
-                table[src] = len(table)
-                parsed.append(PP.parse_pattern(src, rep_max))
-                k.append(PP.tolerance(parsed[-1].Mand, max_dist, max_ratio))
-            jobs.append((b, table[src]))
-            named.append((name, src))
+    k = []
+
+    def parse(src):
+        pattern = PP.parse_pattern(src, rep_max)
+        k.append(PP.tolerance(pattern.Mand, max_dist, max_ratio))
+        return pattern
+    records, pages, parsed, jobs, named = _shape_jobs(records, patterns, 'find_pattern', 'patterns', 'a pattern', field, sep, normalise, parse)
     out = [[] for _ in records]
     if not jobs:
         return out
@@ -168,32 +182,9 @@ def find_regex(records, expressions, field='rec', sep=' ', normalise=None, max_h
     (`\\d+` in `12345 ` is `12345`).  An expression in find_pattern's subset gets the hits find_pattern gives it at k = 0.  A hit that touches
     no word is dropped and counted."""
     from ..utils import page_regex as PR
-    from ..utils.page_search import page_index
-    records = [list(recs) for recs in records]
-    for b, recs in enumerate(records):
-        for r in recs:
-            if not isinstance(r, dict) or 'polys' not in r:
-                raise ValueError('image %d: find_regex needs text-spotting records (dicts with `polys`)' % b)
-    expressions = list(expressions)
-    if expressions and all(isinstance(p, list) for p in expressions):      # a tuple is a (name, string) pair, so per-image lists are LISTS
-        if len(expressions) != len(records):
-            raise ValueError('expressions holds %d lists for %d images' % (len(expressions), len(records)))
-        lists = [list(p) for p in expressions]
-    else:
-        lists = [expressions] * len(records)
-    pages = [page_index(recs, field, sep, normalise) for recs in records]
+    records, pages, parsed, jobs, named = _shape_jobs(records, expressions, 'find_regex', 'expressions', 'an expression', field, sep, normalise,
+                                                      PR.parse_regex)
     fuzzy = max_dist is not None or (max_ratio is not None and float(max_ratio) != 0.0)
-    table, parsed, jobs, named = {}, [], [], []
-    for b, ps in enumerate(lists):
-        for p in ps:
-            name, src = (None, p) if isinstance(p, str) else p if isinstance(p, tuple) and len(p) == 2 else (None, None)
-            if not isinstance(src, str) or not (name is None or isinstance(name, str)):
-                raise ValueError('an expression is a string or a (name, string) pair, got %r' % (p,))
-            if src not in table:
-                table[src] = len(table)
-                parsed.append(PR.parse_regex(src))
-            jobs.append((b, table[src]))
-            named.append((name, src))
     out = [[] for _ in records]
     if not jobs:
         return out

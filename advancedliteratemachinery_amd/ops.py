@@ -971,7 +971,34 @@ def page_align(pool, pool_bytes, a_off, a_len, b_off, b_len, map_off, scratch_of
     return counts.reshape(-1)[:4 * P].view(P, 4)
 
 
-PAGE_SEARCH_CHUNK = 128        # omp_page_search: text columns per lane (csrc/page_search.hip: PS_CHUNK)
+def _page_io(rows, things, jobs, J, H, device, best, n_hits, hits):
+    """what the four page searches share: every (name, tensor, dtype, numel) row is a contiguous device tensor of its type with at least
+    numel elements, jobs holds J (page, `things`) pairs, and best / n_hits / hits are made on `device`, or checked when the caller brings
+    them -> [best, n_hits, hits], flat"""
+    for name, t, dtype, numel in rows:
+        if t is None:
+            raise ValueError('%s is missing' % name)
+        _c(t, name)
+        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
+            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
+    if jobs.numel() != 2 * J:
+        raise ValueError('jobs must hold (page, %s) pairs, got %d integers' % (things, jobs.numel()))
+    outs = []
+    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
+        if t is None:
+            t = torch.empty(max(numel, 1), dtype=torch.int32, device=device)
+        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
+        outs.append(t)
+    return outs
+
+
+def _page_views(outs, J, H):
+    """-> best [J, 2], n_hits [J], hits [J, H, 3]"""
+    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+
+
+PAGE_SEARCH_CHUNK = 128        # omp_page_search: text columns per lane (csrc/page_frame.h: PG_CHUNK)
 PAGE_SEARCH_HIT_BYTES = 512     # omp_page_search: scratch per job and kept hit: 64 lanes x (end, dist)
 
 
@@ -988,30 +1015,16 @@ def page_search(pool, pool_bytes, page_off, page_len, query_off, query_len, k, j
     n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, dist, start), -1 where there is no hit); n_hits = -1 for a job whose lengths,
     ranges or tolerance are out of bounds."""
     P, Q, J, H = int(page_len.numel()), int(query_len.numel()), int(jobs.numel()) // 2, int(max_hits)
-    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
-                                  ('query_off', query_off, torch.int32, Q), ('query_len', query_len, torch.int32, Q), ('k', k, torch.int32, Q),
-                                  ('jobs', jobs, torch.int32, 2 * J), ('scratch', scratch, torch.uint8, 0)):
-        if t is None:
-            raise ValueError('%s is missing' % name)
-        _c(t, name)
-        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
-            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
-    if jobs.numel() != 2 * J:
-        raise ValueError('jobs must hold (page, query) pairs, got %d integers' % jobs.numel())
-    outs = []
-    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
-        if t is None:
-            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
-        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
-            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
-        outs.append(t)
+    outs = _page_io((('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
+                     ('query_off', query_off, torch.int32, Q), ('query_len', query_len, torch.int32, Q), ('k', k, torch.int32, Q),
+                     ('jobs', jobs, torch.int32, 2 * J), ('scratch', scratch, torch.uint8, 0)), 'query', jobs, J, H, page_len.device, best, n_hits, hits)
     rc = _lib.lib().omp_page_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(query_off), ptr(query_len), ptr(k), Q, ptr(jobs), J,
                                     int(sigma), H, ptr(scratch), int(scratch.numel()), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
     _lib.check(rc, 'omp_page_search')
-    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+    return _page_views(outs, J, H)
 
 
-PAGE_PATTERN_CHUNK = 128       # omp_page_pattern_search: text columns per lane (csrc/page_pattern.hip: PP_CHUNK)
+PAGE_PATTERN_CHUNK = 128       # omp_page_pattern_search: text columns per lane (csrc/page_frame.h: PG_CHUNK)
 PAGE_PATTERN_HIT_BYTES = 512    # omp_page_pattern_search: scratch per job and kept hit: 64 lanes x (end, dist)
 
 
@@ -1029,30 +1042,24 @@ def page_pattern_search(pool, pool_bytes, page_off, page_len, masks, opt, pat_le
     end), n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, dist, start), -1 where there is no hit); n_hits = -1 for a job whose
     lengths, ranges, opt word or tolerance are out of bounds."""
     P, Q, J, H, S = int(page_len.numel()), int(pat_len.numel()), int(jobs.numel()) // 2, int(max_hits), int(sigma)
-    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
-                                  ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('opt', opt, torch.int64, Q), ('pat_len', pat_len, torch.int32, Q),
-                                  ('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J), ('scratch', scratch, torch.uint8, 0)):
-        if t is None:
-            raise ValueError('%s is missing' % name)
-        _c(t, name)
-        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
-            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
-    if jobs.numel() != 2 * J:
-        raise ValueError('jobs must hold (page, pattern) pairs, got %d integers' % jobs.numel())
-    outs = []
-    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
-        if t is None:
-            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
-        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
-            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
-        outs.append(t)
+    outs = _page_io((('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
+                     ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('opt', opt, torch.int64, Q), ('pat_len', pat_len, torch.int32, Q),
+                     ('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J), ('scratch', scratch, torch.uint8, 0)), 'pattern', jobs, J, H,
+                    page_len.device, best, n_hits, hits)
     rc = _lib.lib().omp_page_pattern_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(masks), ptr(opt), ptr(pat_len), ptr(k), Q,
                                             ptr(jobs), J, S, H, ptr(scratch), int(scratch.numel()), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
     _lib.check(rc, 'omp_page_pattern_search')
-    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+    return _page_views(outs, J, H)
 
 
-PAGE_REGEX_CHUNK = 128         # omp_page_regex_search: text columns per lane (csrc/page_regex.hip: PR_CHUNK)
+PAGE_REGEX_CHUNK = 128         # omp_page_regex_search: text columns per lane (csrc/page_frame.h: PG_CHUNK)
+
+
+def _regex_rows(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, P, Q, S):
+    """the rows both expression searches check"""
+    return (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
+            ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('first', first, torch.int64, Q), ('last', last, torch.int64, Q),
+            ('follow', follow, torch.int64, 64 * Q), ('pred', pred, torch.int64, 64 * Q), ('pat_len', pat_len, torch.int32, Q))
 
 
 def page_regex_search(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, sigma, max_hits, best=None, n_hits=None,
@@ -1065,59 +1072,27 @@ def page_regex_search(pool, pool_bytes, page_off, page_len, masks, first, last, 
     [J, max_hits, 3] = (end, 0, start), -1 where there is no hit); n_hits = -1 for a job whose lengths, ranges or automaton words are
     out of bounds."""
     P, Q, J, H, S = int(page_len.numel()), int(pat_len.numel()), int(jobs.numel()) // 2, int(max_hits), int(sigma)
-    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
-                                  ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('first', first, torch.int64, Q), ('last', last, torch.int64, Q),
-                                  ('follow', follow, torch.int64, 64 * Q), ('pred', pred, torch.int64, 64 * Q), ('pat_len', pat_len, torch.int32, Q),
-                                  ('jobs', jobs, torch.int32, 2 * J)):
-        if t is None:
-            raise ValueError('%s is missing' % name)
-        _c(t, name)
-        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
-            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
-    if jobs.numel() != 2 * J:
-        raise ValueError('jobs must hold (page, expression) pairs, got %d integers' % jobs.numel())
-    outs = []
-    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
-        if t is None:
-            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
-        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
-            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
-        outs.append(t)
+    rows = _regex_rows(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, P, Q, S)
+    outs = _page_io(rows + (('jobs', jobs, torch.int32, 2 * J),), 'expression', jobs, J, H, page_len.device, best, n_hits, hits)
     rc = _lib.lib().omp_page_regex_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(masks), ptr(first), ptr(last), ptr(follow),
                                           ptr(pred), ptr(pat_len), Q, ptr(jobs), J, S, H, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
     _lib.check(rc, 'omp_page_regex_search')
-    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+    return _page_views(outs, J, H)
 
 
 def page_regex_fuzzy_search(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, k, jobs, sigma, max_hits, best=None,
                             n_hits=None, hits=None):
-    """omp_page_regex_fuzzy_search (csrc/page_regex_fuzzy.hip; utils/page_regex.py holds the specification): the inputs of page_regex_search
+    """omp_page_regex_fuzzy_search (csrc/page_regex.hip; utils/page_regex.py holds the specification): the inputs of page_regex_search
     and k int32 [Q], one tolerance 0 .. 4 per expression; the kernel needs no scratch -> (best int32 [J, 2] = (the least distance, the least
     end that attains it) or (k + 1, 0), n_hits int32 [J], hits int32 [J, max_hits, 3] = (end, dist, start), -1 where there is no hit);
     n_hits = -1 for a job whose lengths, ranges, automaton words or tolerance are out of bounds."""
     P, Q, J, H, S = int(page_len.numel()), int(pat_len.numel()), int(jobs.numel()) // 2, int(max_hits), int(sigma)
-    for name, t, dtype, numel in (('pool', pool, torch.uint8, pool_bytes), ('page_off', page_off, torch.int32, P), ('page_len', page_len, torch.int32, P),
-                                  ('masks', masks, torch.int64, Q * (max(S, 0) + 1)), ('first', first, torch.int64, Q), ('last', last, torch.int64, Q),
-                                  ('follow', follow, torch.int64, 64 * Q), ('pred', pred, torch.int64, 64 * Q), ('pat_len', pat_len, torch.int32, Q),
-                                  ('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J)):
-        if t is None:
-            raise ValueError('%s is missing' % name)
-        _c(t, name)
-        if not t.is_cuda or t.dtype != dtype or t.numel() < numel:
-            raise ValueError('%s must be a device %s tensor with at least %d elements, got %s x %d' % (name, dtype, numel, t.dtype, t.numel()))
-    if jobs.numel() != 2 * J:
-        raise ValueError('jobs must hold (page, expression) pairs, got %d integers' % jobs.numel())
-    outs = []
-    for name, t, numel in (('best', best, 2 * J), ('n_hits', n_hits, J), ('hits', hits, 3 * max(H, 0) * J)):
-        if t is None:
-            t = torch.empty(max(numel, 1), dtype=torch.int32, device=page_len.device)
-        elif not t.is_cuda or t.dtype != torch.int32 or t.numel() < numel or not t.is_contiguous():
-            raise ValueError('%s must be a contiguous device int32 tensor with at least %d elements' % (name, numel))
-        outs.append(t)
+    rows = _regex_rows(pool, pool_bytes, page_off, page_len, masks, first, last, follow, pred, pat_len, P, Q, S)
+    outs = _page_io(rows + (('k', k, torch.int32, Q), ('jobs', jobs, torch.int32, 2 * J)), 'expression', jobs, J, H, page_len.device, best, n_hits, hits)
     rc = _lib.lib().omp_page_regex_fuzzy_search(ptr(pool), int(pool_bytes), ptr(page_off), ptr(page_len), P, ptr(masks), ptr(first), ptr(last), ptr(follow),
                                                 ptr(pred), ptr(pat_len), ptr(k), Q, ptr(jobs), J, S, H, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream())
     _lib.check(rc, 'omp_page_regex_fuzzy_search')
-    return outs[0][:2 * J].view(J, 2), outs[1][:J], outs[2][:3 * H * J].view(J, H, 3)
+    return _page_views(outs, J, H)
 
 
 def _reading_tables(polys, tables, host_tables, n_groups):

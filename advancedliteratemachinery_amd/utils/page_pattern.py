@@ -34,9 +34,9 @@ import numpy as np
 from .page_search import HITS_MAX, JOBS_MAX, SCRATCH_CAP, hit_ends
 from .page_text import LEN_MAX, SIGMA_MAX, _DeviceStage
 
-POS_MAX = 64                    # positions a pattern (csrc/page_pattern.hip: PP_POS_MAX): one 64-bit word per row
+POS_MAX = 64                    # positions a pattern (csrc/page_frame.h: PG_POS_MAX): one 64-bit word per row
 K_MAX = 8                       # errors at the most (csrc/page_pattern.hip: PP_K_MAX): k + 1 <= 9 rows live in registers
-CHUNK = 128                     # text columns per lane (csrc/page_pattern.hip: PP_CHUNK)
+CHUNK = 128                     # text columns per lane (csrc/page_frame.h: PG_CHUNK)
 _FULL = (1 << 64) - 1
 
 
@@ -484,29 +484,9 @@ class PatternSearcher(_DeviceStage):
 
     def run(self, pool, page_off, page_len, masks, opt, pat_len, jobs, k, max_hits):
         """the inputs of search_cpu -> the dict of search_cpu, as numpy.  sigma is masks.shape[1] - 1."""
-        import torch
-
         from .. import ops
         pool, po, pl, masks, opt, P, jobs, k, H = _check_search(pool, page_off, page_len, masks, opt, pat_len, jobs, k, max_hits)
-        sigma = masks.shape[1] - 1
-        J = jobs.shape[0]
-        self.calls += 1
-        parts = chunk_jobs(J, H, self.scratch_cap)
-        self.chunks = len(parts)
-        if J == 0:
-            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
-        with torch.cuda.device(self.device):
-            # the 64-bit words travel as int64: the same bytes
-            (d_masks, d_opt, d_po, d_pl, d_P, d_k, d_jobs), d_pool = self._upload((masks.reshape(-1).view(np.int64), opt.view(np.int64), po, pl, P, k,
-                                                                                   jobs.reshape(-1)), pool)
-            scratch = self._grow(ops.page_pattern_scratch_bytes(max(hi - lo for lo, hi in parts), H))
-            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
-            for lo, hi in parts:
-                ops.page_pattern_search(d_pool, pool.size, d_po, d_pl, d_masks, d_opt, d_P, d_k, d_jobs[2 * lo:2 * hi], sigma, H, scratch,
-                                        best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
-            host = out.cpu().numpy()                                          # the one download
-        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
-        if (res['n_hits'] < 0).any():
-            raise RuntimeError('omp_page_pattern_search refused a job (a length above the limits, a range outside the pool, opt bits at or above P, '
-                               'or k above min(Mand - 1, %d))' % K_MAX)
-        return res
+        return self._search(ops.page_pattern_search, (po, pl, masks, opt, P, k), pool, jobs, masks.shape[1] - 1, H,
+                            chunk_jobs(jobs.shape[0], H, self.scratch_cap),
+                            'omp_page_pattern_search refused a job (a length above the limits, a range outside the pool, opt bits at or above P, '
+                            'or k above min(Mand - 1, %d))' % K_MAX, ops.page_pattern_scratch_bytes)

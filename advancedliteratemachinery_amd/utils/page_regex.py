@@ -28,7 +28,7 @@ Split       ends_chunked(): the kernel's way over a page.  The step is linear ov
             chunk WITHOUT injecting first, until no lane gets a new bit.
 Limits      a page 0 .. 65535 characters, 1 .. 2^20 jobs a call, 1 .. 64 hits kept per job.
 
-With errors (csrc/page_regex_fuzzy.hip, omp_page_regex_fuzzy_search, equals fuzzy_search_cpu on every integer):
+With errors (csrc/page_regex.hip, omp_page_regex_fuzzy_search, equals fuzzy_search_cpu on every integer):
 Tolerance   k = regex_tolerance(min_len, max_dist, max_ratio) = min(page_pattern.tolerance(min_len, ...), K_MAX), min_len the length of the
             shortest word of the language: k <= min_len - 1, so deleting the whole expression never qualifies.
 Rows        R_0 .. R_k, one word each.  Bit p of R_i after column j: some t[s:j] aligns, with at most i insertions, deletions and
@@ -53,11 +53,11 @@ from .page_pattern import _ANCHOR_ESCAPES, _CLASS_ESCAPES, _compiled, encode_cla
 from .page_search import HITS_MAX, JOBS_MAX, hit_ends
 from .page_text import LEN_MAX, SIGMA_MAX, _DeviceStage
 
-POS_MAX = 64                    # positions an expression (csrc/page_regex.hip: PR_POS_MAX): one 64-bit state word
-CHUNK = 128                     # text columns per lane (csrc/page_regex.hip: PR_CHUNK)
+POS_MAX = 64                    # positions an expression (csrc/page_frame.h: PG_POS_MAX): one 64-bit state word
+CHUNK = 128                     # text columns per lane (csrc/page_frame.h: PG_CHUNK)
 LANES = 64
 ROUND = CHUNK * LANES           # text columns per round of the wave
-K_MAX = 4                       # errors at the most under an expression (csrc/page_regex_fuzzy.hip: PF_K_MAX): k + 1 <= 5 rows in registers
+K_MAX = 4                       # errors at the most under an expression (csrc/page_regex.hip: PR_K_MAX): k + 1 <= 5 rows in registers
 _FULL = (1 << 64) - 1
 
 
@@ -545,6 +545,11 @@ class HostRegexSearcher(object):
 # ---------------------------------------------------------------------------------------------
 # the device stage
 # ---------------------------------------------------------------------------------------------
+def _job_parts(n_jobs):
+    """-> [(lo, hi)]: the kernels need no scratch, so a launch takes JOBS_MAX jobs"""
+    return [(lo, min(lo + JOBS_MAX, n_jobs)) for lo in range(0, n_jobs, JOBS_MAX)]
+
+
 class RegexSearcher(_DeviceStage):
     """search_cpu on the device.  A call is ONE packed upload of the tables and the pool, one omp_page_regex_search launch per JOBS_MAX
     jobs (the kernel needs no scratch), and ONE download of best, n_hits and hits.  There is no CPU fallback: HostRegexSearcher is the
@@ -556,33 +561,13 @@ class RegexSearcher(_DeviceStage):
 
     def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, max_hits):
         """the inputs of search_cpu -> the dict of search_cpu, as numpy.  sigma is masks.shape[1] - 1."""
-        import torch
-
         from .. import ops
         pool, po, pl, masks, first, last, follow, pred, P, jobs, H = _check_search(pool, page_off, page_len, masks, first, last, follow, pred,
                                                                                    pat_len, jobs, max_hits)
-        sigma = masks.shape[1] - 1
-        J = jobs.shape[0]
-        self.calls += 1
-        parts = [(lo, min(lo + JOBS_MAX, J)) for lo in range(0, J, JOBS_MAX)]
-        self.chunks = len(parts)
-        if J == 0:
-            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
-        with torch.cuda.device(self.device):
-            # the 64-bit words travel as int64: the same bytes
-            i64 = lambda a: a.reshape(-1).view(np.int64)                        # noqa: E731
-            (d_masks, d_first, d_last, d_follow, d_pred, d_po, d_pl, d_P, d_jobs), d_pool = self._upload(
-                (i64(masks), i64(first), i64(last), i64(follow), i64(pred), po, pl, P, jobs.reshape(-1)), pool)
-            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
-            for lo, hi in parts:
-                ops.page_regex_search(d_pool, pool.size, d_po, d_pl, d_masks, d_first, d_last, d_follow, d_pred, d_P, d_jobs[2 * lo:2 * hi], sigma, H,
-                                      best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
-            host = out.cpu().numpy()                                          # the one download
-        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
-        if (res['n_hits'] < 0).any():
-            raise RuntimeError('omp_page_regex_search refused a job (a length above the limits, a range outside the pool, or first, last, follow '
-                               'or pred words with bits or rows at or above P)')
-        return res
+        return self._search(ops.page_regex_search, (po, pl, masks, first, last, follow, pred, P), pool, jobs, masks.shape[1] - 1, H,
+                            _job_parts(jobs.shape[0]),
+                            'omp_page_regex_search refused a job (a length above the limits, a range outside the pool, or first, last, follow '
+                            'or pred words with bits or rows at or above P)')
 
 
 # ---------------------------------------------------------------------------------------------
@@ -814,29 +799,10 @@ class FuzzyRegexSearcher(_DeviceStage):
 
     def run(self, pool, page_off, page_len, masks, first, last, follow, pred, pat_len, jobs, k, max_hits):
         """the inputs of fuzzy_search_cpu -> the dict of fuzzy_search_cpu, as numpy.  sigma is masks.shape[1] - 1."""
-        import torch
-
         from .. import ops
         pool, po, pl, masks, first, last, follow, pred, P, jobs, k, H = _check_fuzzy(pool, page_off, page_len, masks, first, last, follow, pred,
                                                                                      pat_len, jobs, k, max_hits)
-        sigma = masks.shape[1] - 1
-        J = jobs.shape[0]
-        self.calls += 1
-        parts = [(lo, min(lo + JOBS_MAX, J)) for lo in range(0, J, JOBS_MAX)]
-        self.chunks = len(parts)
-        if J == 0:
-            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
-        with torch.cuda.device(self.device):
-            i64 = lambda a: a.reshape(-1).view(np.int64)                        # noqa: E731  the 64-bit words travel as int64: the same bytes
-            (d_masks, d_first, d_last, d_follow, d_pred, d_po, d_pl, d_P, d_k, d_jobs), d_pool = self._upload(
-                (i64(masks), i64(first), i64(last), i64(follow), i64(pred), po, pl, P, k, jobs.reshape(-1)), pool)
-            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
-            for lo, hi in parts:
-                ops.page_regex_fuzzy_search(d_pool, pool.size, d_po, d_pl, d_masks, d_first, d_last, d_follow, d_pred, d_P, d_k, d_jobs[2 * lo:2 * hi], sigma,
-                                            H, best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
-            host = out.cpu().numpy()                                          # the one download
-        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
-        if (res['n_hits'] < 0).any():
-            raise RuntimeError('omp_page_regex_fuzzy_search refused a job (a length above the limits, a range outside the pool, first, last, '
-                               'follow or pred words with bits or rows at or above P, or k outside 0 .. %d)' % K_MAX)
-        return res
+        return self._search(ops.page_regex_fuzzy_search, (po, pl, masks, first, last, follow, pred, P, k), pool, jobs, masks.shape[1] - 1, H,
+                            _job_parts(jobs.shape[0]),
+                            'omp_page_regex_fuzzy_search refused a job (a length above the limits, a range outside the pool, first, last, '
+                            'follow or pred words with bits or rows at or above P, or k outside 0 .. %d)' % K_MAX)

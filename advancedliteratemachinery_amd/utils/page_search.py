@@ -24,7 +24,7 @@ import numpy as np
 from .page_text import LEN_MAX, NONE, SIGMA_MAX, _DeviceStage, _encode, _rows
 
 QUERY_MAX = 64                  # characters a query (csrc/page_search.hip: PS_QUERY_MAX): one 64-bit word of Myers' column
-CHUNK = 128                     # text columns per lane (csrc/page_search.hip: PS_CHUNK)
+CHUNK = 128                     # text columns per lane (csrc/page_frame.h: PG_CHUNK)
 HITS_MAX = 64                   # hits kept per job at the most
 JOBS_MAX = 1 << 20
 SCRATCH_CAP = 1 << 28           # device scratch per chunk of jobs
@@ -245,8 +245,6 @@ class PageSearcher(_DeviceStage):
     def run(self, pool, page_off, page_len, query_off, query_len, jobs, k, max_hits, sigma=None):
         """the inputs of search_cpu (sigma: the number of dense codes; None: the largest code of the pool below 255, plus one) -> the
         dict of search_cpu, as numpy"""
-        import torch
-
         from .. import ops
         pool, po, pl, qo, ql, jobs, k, H = _check_search(pool, page_off, page_len, query_off, query_len, jobs, k, max_hits)
         dense = pool[pool != NONE]
@@ -254,21 +252,5 @@ class PageSearcher(_DeviceStage):
         sigma = top if sigma is None else int(sigma)
         if sigma < top or sigma > SIGMA_MAX:
             raise ValueError('sigma must be %d .. %d for this pool, got %d' % (top, SIGMA_MAX, sigma))
-        J, P, Q = jobs.shape[0], pl.size, ql.size
-        self.calls += 1
-        parts = chunk_jobs(J, H, self.scratch_cap)
-        self.chunks = len(parts)
-        if J == 0:
-            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
-        with torch.cuda.device(self.device):
-            (d_po, d_pl, d_qo, d_ql, d_k, d_jobs), d_pool = self._upload((po, pl, qo, ql, k, jobs.reshape(-1)), pool)
-            scratch = self._grow(ops.page_search_scratch_bytes(max(hi - lo for lo, hi in parts), H))
-            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
-            for lo, hi in parts:
-                ops.page_search(d_pool, pool.size, d_po, d_pl, d_qo, d_ql, d_k, d_jobs[2 * lo:2 * hi], sigma, H, scratch,
-                                best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi], hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
-            host = out.cpu().numpy()                                          # the one download
-        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
-        if (res['n_hits'] < 0).any():
-            raise RuntimeError('omp_page_search refused a job (a length above the limits, a range outside the pool, or k >= m)')
-        return res
+        return self._search(ops.page_search, (po, pl, qo, ql, k), pool, jobs, sigma, H, chunk_jobs(jobs.shape[0], H, self.scratch_cap),
+                            'omp_page_search refused a job (a length above the limits, a range outside the pool, or k >= m)', ops.page_search_scratch_bytes)

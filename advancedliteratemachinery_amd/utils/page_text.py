@@ -207,8 +207,9 @@ def _check_sigma(pool, sigma):
 
 
 class _DeviceStage(object):
-    """what PageTextScorer, page_search.PageSearcher and page_align.PageAligner share: the device check, the cached scratch and the
-    packed upload.  HOST names the host twin, the specification."""
+    """what PageTextScorer, page_align.PageAligner and the searchers of page_search, page_pattern and page_regex share: the device check,
+    the cached scratch and the packed upload; the searchers also the whole device half of their `run` (_search).  HOST names the host
+    twin, the specification."""
     HOST = None
 
     def __init__(self, device, scratch_cap):
@@ -237,6 +238,38 @@ class _DeviceStage(object):
         blob = torch.from_numpy(np.concatenate([t.view(np.uint8) for t in tables] + [pool, np.zeros(1, np.uint8)])).to(self.device)
         ends = np.cumsum([t.nbytes for t in tables]).tolist()
         return [blob[e - t.nbytes:e].view(getattr(torch, t.dtype.name)) for t, e in zip(tables, ends)], blob[ends[-1]:]
+
+    def _search(self, op, tables, pool, jobs, sigma, H, parts, refused, scratch_bytes=None):
+        """the device half of a page search's `run` (page_search, page_pattern and page_regex).  op: the ops wrapper, which takes (pool,
+        pool_bytes, *tables, jobs, sigma, max_hits[, scratch], best=, n_hits=, hits=); tables: numpy, in the wrapper's order (64-bit words
+        travel as int64: the same bytes); jobs int32 [J, 2].  ONE packed upload, the widest tables first; the cached scratch grown to
+        scratch_bytes(the jobs of the largest part, H) when a per-job scratch size is given; one op per (lo, hi) of `parts` with that
+        part's jobs and its slices of the outputs; ONE download -> dict(best int32 [J, 2], n_hits int32 [J], hits int32 [J, H, 3]) as
+        numpy.  A refused job (n_hits < 0) raises RuntimeError(refused)."""
+        import torch
+        J = jobs.shape[0]
+        self.calls += 1
+        self.chunks = len(parts)
+        if J == 0:
+            return dict(best=np.zeros((0, 2), np.int32), n_hits=np.zeros(0, np.int32), hits=np.zeros((0, H, 3), np.int32))
+        flat = [t.reshape(-1).view(np.int64) if t.dtype == np.uint64 else t.reshape(-1) for t in tables] + [jobs.reshape(-1)]
+        order = sorted(range(len(flat)), key=lambda i: -flat[i].itemsize)     # stable
+        with torch.cuda.device(self.device):
+            sent, d_pool = self._upload([flat[i] for i in order], pool)
+            tabs = [None] * len(flat)
+            for i, d in zip(order, sent):
+                tabs[i] = d                                                   # back in the wrapper's order
+            d_jobs = tabs.pop()
+            tail = () if scratch_bytes is None else (self._grow(scratch_bytes(max(hi - lo for lo, hi in parts), H)),)
+            out = torch.empty(J * (3 + 3 * H), dtype=torch.int32, device=self.device)     # best [J, 2] | n_hits [J] | hits [J, H, 3]
+            for lo, hi in parts:
+                op(d_pool, pool.size, *tabs, d_jobs[2 * lo:2 * hi], sigma, H, *tail, best=out[2 * lo:2 * hi], n_hits=out[2 * J + lo:2 * J + hi],
+                   hits=out[3 * J + 3 * H * lo:3 * J + 3 * H * hi])
+            host = out.cpu().numpy()                                          # the one download
+        res = dict(best=host[:2 * J].reshape(J, 2), n_hits=host[2 * J:3 * J], hits=host[3 * J:].reshape(J, H, 3))
+        if (res['n_hits'] < 0).any():
+            raise RuntimeError(refused)
+        return res
 
 
 class PageTextScorer(_DeviceStage):

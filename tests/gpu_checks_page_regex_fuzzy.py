@@ -296,20 +296,52 @@ def check_limit():
                 0 if rows == [(62, 4, 0), (2 * R + 32, 3, 2 * R - 31), (30064, 2, 30000), (n, 4, n - 68)] else 1, 0, str(rows))]
 
 
+def exact_cases():
+    """k = 0 on planted texts: -> (texts, expressions, [(what, page, expression, the hits it must have)])"""
+    lit = 'abcdef'
+    texts = [_planted(R + 100, [(R - 5, lit)]), _planted(R + 100, [(R - 3, '7' * 7)]), _planted(R, [(R - 5, lit)])]
+    return texts, [lit, r'\d+'], [('a pending end at column 8192 that is a hit', 0, 0, [(R, 0, R - 6)]),
+                                  ('a pending end at column 8192 inside a run of ends', 1, 1, [(R + 3, 0, R - 4)]),
+                                  ('an end at n = 8192, which is not pending', 2, 0, [(R, 0, R - 6)]),
+                                  ('a page without an end', 0, 1, [])]
+
+
 def check_exact():
-    """k = 0: the ends and starts of omp_page_regex_search on the same jobs"""
+    """k = 0: omp_page_regex_search launches the instance of the kernel that holds one row only, omp_page_regex_fuzzy_search at k = 0 the one
+    that dispatches over k; both against each other and against search_cpu on every integer.  The edge jobs hold every P of POS (so
+    every NB) and texts of 0, 1, 127 .. 129, 255 .. 257 and 8191 .. 8193 characters (check_edges asserts that); the planted jobs hold a
+    pending end at column 8192 that is a hit, one that is none, an end at n = 8192, and one refused job."""
     from advancedliteratemachinery_amd import ops
     from tests.gpu_checks import rec
+
+    def both(packed):
+        d = _device(packed)
+        J, sigma = packed[9].shape[0], packed[3].shape[1] - 1
+        best, n_hits, hits = ops.page_regex_search(d['pool'], packed[0].size, d['po'], d['pl'], d['masks'], d['first'], d['last'], d['follow'], d['pred'], d['P'], d['jobs'], sigma, 64)
+        return dict(best=best.cpu().numpy(), n_hits=n_hits.cpu().numpy(), hits=hits.cpu().numpy()), run_raw(packed, np.zeros(packed[8].size, np.int32), 64, d)
     E = edge_reference()
     packed = E['packed']
-    d = _device(packed)
-    J, sigma = packed[9].shape[0], packed[3].shape[1] - 1
-    best, n_hits, hits = ops.page_regex_search(d['pool'], packed[0].size, d['po'], d['pl'], d['masks'], d['first'], d['last'], d['follow'], d['pred'], d['P'], d['jobs'], sigma, 64)
-    exact = dict(best=best.cpu().numpy(), n_hits=n_hits.cpu().numpy(), hits=hits.cpu().numpy())
-    got = run_raw(packed, np.zeros_like(E['k']), 64, d)
-    return [rec('page regex fuzzy at k = 0 == omp_page_regex_search on the %d edge jobs: best, n_hits, ends and starts' % J, _bad(got, exact), 0,
-                '%d hits' % int(exact['n_hits'].sum())),
-            rec('page regex fuzzy at k = 0: the jobs hold hits', 0 if int((exact['n_hits'] > 0).sum()) > 20 else 1, 0)]
+    if 'exact' not in E:
+        E['exact'] = PR.search_cpu(*packed, 64)
+    exact, got = both(packed)
+    J = packed[9].shape[0]
+    out = [rec('page regex fuzzy at k = 0 == omp_page_regex_search on the %d edge jobs: best, n_hits, ends and starts' % J, _bad(got, exact), 0,
+               '%d hits' % int(exact['n_hits'].sum())),
+           rec('page regex at one row == search_cpu on the %d edge jobs' % J, _bad(exact, E['exact']), 0),
+           rec('page regex fuzzy at k = 0: the jobs hold hits', 0 if int((exact['n_hits'] > 0).sum()) > 20 else 1, 0)]
+    texts, exprs, jobs = exact_cases()
+    planted, _ = from_strings(texts, exprs, [(p, q) for _, p, q, _ in jobs], 0)
+    want = PR.search_cpu(*planted, 64)
+    for j, (what, _, _, hits) in enumerate(jobs):
+        rows = [tuple(r) for r in want['hits'][j].tolist() if r[0] >= 0]
+        out.append(rec('page regex at k = 0[%s]: the definition holds the planted hits' % what, 0 if rows == hits else 1, 0, '%s, planted %s' % (rows[:4], hits)))
+    refused = list(planted)
+    refused[9] = np.concatenate([planted[9], np.asarray([[len(texts), 0]], np.int32)])       # a page that is not there
+    want = {key: np.concatenate([v, np.full((1,) + v.shape[1:], -1, v.dtype)]) for key, v in want.items()}
+    exact, got = both(refused)
+    out.append(rec('page regex at one row == search_cpu on the planted jobs, the refused job -1', _bad(exact, want), 0, str(exact['n_hits'].tolist())))
+    out.append(rec('page regex fuzzy at k = 0 == omp_page_regex_search on the planted jobs and the refused one', _bad(got, exact), 0, str(got['n_hits'].tolist())))
+    return out
 
 
 def check_ordering():

@@ -51,6 +51,10 @@ def test_page_regex_fuzzy_at_the_length_limit(C):
 
 @pytest.mark.timeout(120, method='thread')
 def test_k_0_gives_the_ends_and_starts_of_the_exact_kernel(C):
+    """the exact entry point launches the instance of the expression kernel that holds one row, the entry point with errors the one that
+    dispatches over k: both at k = 0 against each other and against search_cpu, on the edge jobs (every P, so every byte-table count; texts
+    of 0, 1, 127 .. 129, 255 .. 257 and 8191 .. 8193 characters), on a pending end at column 8192 that is a hit and one that is none, and on
+    one refused job"""
     _assert_all(C.check_exact())
 
 

@@ -378,10 +378,11 @@ def test_entry_point_matches_the_header():
     assert 'page_pattern.hip' in build.SOURCES and 'page_pattern.hip' not in build.AUDITED
     assert callable(ops.page_pattern_search) and callable(ops.page_pattern_scratch_bytes)
     src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_pattern.hip')).read()
-    assert 'extern "C" int omp_page_pattern_search(' in src
-    assert 'PP_LEN_MAX = %d' % PP.LEN_MAX in src and 'PP_POS_MAX = %d' % PP.POS_MAX in src and 'PP_CHUNK = %d' % PP.CHUNK in src and 'PP_K_MAX = %d' % PP.K_MAX in src
-    assert 'PP_HITS_MAX = %d' % PS.HITS_MAX in src and 'PP_SIGMA_MAX = %d' % PP.SIGMA_MAX in src
-    assert 'PP_JOBS_MAX = 1 << 20' in src and PS.JOBS_MAX == 1 << 20 and ops.PAGE_PATTERN_CHUNK == PP.CHUNK
+    hdr = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_frame.h')).read()       # the shared constants: test_page_search_host.py
+    assert 'extern "C" int omp_page_pattern_search(' in src and '#include "page_frame.h"' in src
+    assert 'PG_LEN_MAX = %d' % PP.LEN_MAX in hdr and 'PG_POS_MAX = %d' % PP.POS_MAX in hdr and 'PG_CHUNK = %d' % PP.CHUNK in hdr and 'PP_K_MAX = %d' % PP.K_MAX in src
+    assert 'PG_HITS_MAX = %d' % PS.HITS_MAX in hdr and 'PG_SIGMA_MAX = %d' % PP.SIGMA_MAX in hdr
+    assert 'PG_JOBS_MAX = 1 << 20' in hdr and PS.JOBS_MAX == 1 << 20 and ops.PAGE_PATTERN_CHUNK == PP.CHUNK
     assert ops.page_pattern_scratch_bytes(3, 16) == 3 * 16 * 64 * 8 == 3 * 16 * ops.PAGE_PATTERN_HIT_BYTES
     assert PP.chunk_jobs(10, 16, 3 * 16 * 512 + 5) == [(0, 3), (3, 6), (6, 9), (9, 10)] and PP.chunk_jobs(0, 16) == []
     with pytest.raises(ValueError):

@@ -343,10 +343,12 @@ def test_entry_point_matches_the_header():
     assert res is ctypes.c_int and args == want and len(want) == 21 and 'omp_page_regex_fuzzy_search' in _lib.EXPORTS
     exact = _lib._SIGS['omp_page_regex_search'][1]
     assert args == exact[:11] + [ctypes.c_void_p] + exact[11:]                 # omp_page_regex_search's arguments plus k
-    assert 'page_regex_fuzzy.hip' in build.SOURCES and 'page_regex_fuzzy.hip' not in build.AUDITED and callable(ops.page_regex_fuzzy_search)
-    src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_regex_fuzzy.hip')).read()
-    assert 'extern "C" int omp_page_regex_fuzzy_search(' in src and 'PF_K_MAX = %d' % PR.K_MAX in src
-    assert 'PF_LEN_MAX = %d' % PP.LEN_MAX in src and 'PF_POS_MAX = %d' % PR.POS_MAX in src and 'PF_CHUNK = %d' % PR.CHUNK in src
-    assert 'PF_HITS_MAX = %d' % PS.HITS_MAX in src and 'PF_SIGMA_MAX = %d' % PP.SIGMA_MAX in src and 'PF_JOBS_MAX = 1 << 20' in src
+    # the unit is the exact search's: the kernel at k = 0 is the exact kernel
+    assert 'page_regex.hip' in build.SOURCES and 'page_regex.hip' not in build.AUDITED and callable(ops.page_regex_fuzzy_search)
+    src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_regex.hip')).read()
+    hdr = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_frame.h')).read()       # the shared constants: test_page_search_host.py
+    assert 'extern "C" int omp_page_regex_fuzzy_search(' in src and 'PR_K_MAX = %d' % PR.K_MAX in src and 'pr_launch<PR_K_MAX + 1>' in src
+    assert 'PG_LEN_MAX = %d' % PP.LEN_MAX in hdr and 'PG_POS_MAX = %d' % PR.POS_MAX in hdr and 'PG_CHUNK = %d' % PR.CHUNK in hdr
+    assert 'PG_HITS_MAX = %d' % PS.HITS_MAX in hdr and 'PG_SIGMA_MAX = %d' % PP.SIGMA_MAX in hdr and 'PG_JOBS_MAX = 1 << 20' in hdr
     with pytest.raises(RuntimeError):
         PR.FuzzyRegexSearcher('cpu')

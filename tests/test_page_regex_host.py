@@ -323,9 +323,10 @@ def test_entry_point_matches_the_header():
     assert 'page_regex.hip' in build.SOURCES and 'page_regex.hip' not in build.AUDITED
     assert callable(ops.page_regex_search) and not hasattr(ops, 'page_regex_scratch_bytes')         # the kernel needs no scratch
     src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_regex.hip')).read()
-    assert 'extern "C" int omp_page_regex_search(' in src
-    assert 'PR_LEN_MAX = %d' % PP.LEN_MAX in src and 'PR_POS_MAX = %d' % PR.POS_MAX in src and 'PR_CHUNK = %d' % PR.CHUNK in src
-    assert 'PR_HITS_MAX = %d' % PS.HITS_MAX in src and 'PR_SIGMA_MAX = %d' % PP.SIGMA_MAX in src and 'PR_JOBS_MAX = 1 << 20' in src
+    hdr = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_frame.h')).read()       # the shared constants: test_page_search_host.py
+    assert 'extern "C" int omp_page_regex_search(' in src and '#include "page_frame.h"' in src
+    assert 'PG_LEN_MAX = %d' % PP.LEN_MAX in hdr and 'PG_POS_MAX = %d' % PR.POS_MAX in hdr and 'PG_CHUNK = %d' % PR.CHUNK in hdr
+    assert 'PG_HITS_MAX = %d' % PS.HITS_MAX in hdr and 'PG_SIGMA_MAX = %d' % PP.SIGMA_MAX in hdr and 'PG_JOBS_MAX = 1 << 20' in hdr
     assert PR.ROUND == 64 * PR.CHUNK == 8192 and PR.LANES == 64 and ops.PAGE_REGEX_CHUNK == PR.CHUNK
     with pytest.raises(RuntimeError):
         PR.RegexSearcher('cpu')

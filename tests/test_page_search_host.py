@@ -328,11 +328,26 @@ def test_entry_point_matches_the_header():
     assert res is ctypes.c_int and args == want and len(want) == 19 and 'omp_page_search' in _lib.EXPORTS
     assert 'page_search.hip' in build.SOURCES and 'page_search.hip' not in build.AUDITED
     assert callable(ops.page_search) and callable(ops.page_search_scratch_bytes)
-    src = open(os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc', 'page_search.hip')).read()
+    csrc = os.path.join(ROOT, 'advancedliteratemachinery_amd', 'csrc')
+    src = open(os.path.join(csrc, 'page_search.hip')).read()
     assert 'extern "C" int omp_page_search(' in src
-    assert 'PS_LEN_MAX = %d' % PS.LEN_MAX in src and 'PS_QUERY_MAX = %d' % PS.QUERY_MAX in src and 'PS_CHUNK = %d' % PS.CHUNK in src
-    assert 'PS_HITS_MAX = %d' % PS.HITS_MAX in src and 'PS_SIGMA_MAX = %d' % PS.SIGMA_MAX in src and 'PS_NONE = %d' % PS.NONE in src
-    assert 'PS_JOBS_MAX = 1 << 20' in src and PS.JOBS_MAX == 1 << 20 and ops.PAGE_SEARCH_CHUNK == PS.CHUNK
+    # the frame and its constants are page_frame.h's: the four page-search units take them from there, and none keeps a copy
+    hdr = open(os.path.join(csrc, 'page_frame.h')).read()
+    assert 'page_frame.h' in [os.path.basename(h) for h in build.HEADERS] and '#include "page_frame.h"' in src
+    assert 'PG_LEN_MAX = %d' % PS.LEN_MAX in hdr and 'PS_QUERY_MAX = %d' % PS.QUERY_MAX in src and 'PG_CHUNK = %d' % PS.CHUNK in hdr
+    assert 'PG_HITS_MAX = %d' % PS.HITS_MAX in hdr and 'PG_SIGMA_MAX = %d' % PS.SIGMA_MAX in hdr and 'PS_NONE = %d' % PS.NONE in src
+    assert 'PG_POS_MAX = %d' % PS.QUERY_MAX in hdr and 'PS_QUERY_MAX == PG_POS_MAX' in src
+    assert 'PG_JOBS_MAX = 1 << 20' in hdr and PS.JOBS_MAX == 1 << 20 and ops.PAGE_SEARCH_CHUNK == PS.CHUNK
+    assert 'PG_ROUND = 64 * PG_CHUNK' in hdr
+    for unit in ('page_search.hip', 'page_pattern.hip', 'page_regex.hip'):
+        text = open(os.path.join(csrc, unit)).read()
+        assert '#include "page_frame.h"' in text and unit in build.SOURCES
+        assert not re.search(r'\bPG_\w+\s*=[^=]', text), unit                                         # no unit redefines a shared constant
+        assert not re.search(r'\bP[SPRF]_(LEN_MAX|POS_MAX|CHUNK|HITS_MAX|SIGMA_MAX|JOBS_MAX|ROUND)\b', text), unit   # nor keeps its own copy
+    # the search with errors is the exact search's unit: one source, both entry points
+    assert 'page_regex_fuzzy.hip' not in build.SOURCES and not os.path.exists(os.path.join(csrc, 'page_regex_fuzzy.hip'))
+    regex = open(os.path.join(csrc, 'page_regex.hip')).read()
+    assert 'extern "C" int omp_page_regex_search(' in regex and 'extern "C" int omp_page_regex_fuzzy_search(' in regex
     assert ops.page_search_scratch_bytes(3, 16) == 3 * 16 * 64 * 8 == 3 * 16 * ops.PAGE_SEARCH_HIT_BYTES
     assert PS.chunk_jobs(10, 16, 3 * 16 * 512 + 5) == [(0, 3), (3, 6), (6, 9), (9, 10)] and PS.chunk_jobs(0, 16) == []
     with pytest.raises(ValueError):
